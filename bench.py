@@ -2,7 +2,7 @@
 DualEncoder + "cross_attention" (= mean fusion in the reference) training
 step on the HIP engine, 1..8 MI355X (BASELINE.json metric / configs[2]).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,11 @@ A step = Trainer.train_step on one pre-staged synthetic phantom batch
 accumulation_steps=1, dropout 0, bf16 activations / fp32 params+grads.
 Per-GPU batch is fixed (weak scaling); value = N*B*K / max-over-ranks time.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (patches/s, ms_per_step, loss).  --full adds
+what takes runs of its own: the per-kernel-family timer window and the roofline read from it and from the committed
+profile summaries, and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned and left
+behind (loss, a seeded sample of the updated parameters) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -312,6 +317,26 @@ def bench_infer(args, trainer, model, mods, dev):
                    "model": args.model, "volumes": V, "size": S, "roi": [96, 96, 96], "sw_batch": 4,
                    "overlap": 0.5},
         "out_finite": bool(torch.isfinite(out).all().item())}), flush=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": out})
+
+
+DUMP_BYTES = 16 << 20     # --dump-outputs writes at most this much in all (float32)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor as path/<name>.npy in float32.  An array over its share of DUMP_BYTES is cut to
+    a fixed sample (seeded element indices, ascending; the same for every run of the same shapes) and stored 1-D."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(977)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -326,6 +351,14 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--modalities", default="CT,PET", help="c5: CT,PET,MRI")
     ap.add_argument("--loss", default="dice_ce", choices=["dice_ce", "tversky"], help="c5: tversky")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the per-kernel-family timer window "
+                         "(--timer-steps, --timer-dump) with the roofline / profile fields, and the CPU baseline "
+                         "(--cpu-steps, --cpu-threads, --no-cpu-baseline); without it those fields are null / empty")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): "
+                         "loss, and params, a seeded sample of the model's parameters after that step (--infer: "
+                         "logits, a seeded sample of the last call's output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: this process's CPU share (cpu_threads())")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed oracle steps in the CPU baseline")
@@ -357,6 +390,13 @@ def main():
     ap.add_argument("--workload-out", default="", help="write this run's workload key (JSON) for the profile "
                                                        "summaries of tools/rocprof_families.py")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.timer_dump and not args.full:
+        ap.error("--timer-dump needs the timer window of --full")
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.timer_steps = 0
     global WORKLOAD
     WORKLOAD = workload_key(args.model, len(args.modalities.split(",")), args.size, args.batch, args.dtype, args.loss,
                             args.fp8, args.kernels)
@@ -434,6 +474,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     loss_val = float(last.item()) if last is not None else float("nan")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "loss": last, "params": torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])})
 
     # per-kernel-family timing over a separate live window: eager steps (a captured graph has no per-launch
     # timing) whose every library kernel is launched with hipExtLaunchKernelGGL start / stop events, stamped by
@@ -453,7 +496,7 @@ def main():
     dom = max(mfma.items(), key=lambda kv: kv[1]["ms"]) if mfma else None
     # ... chosen by rocprofv3 time per step of the captured step where a committed steady-state trace summary
     # names the family (tools/rocprof_families.py uses the timer's family names), else by the timer's own time
-    steady, _ = _profile("steady")
+    steady = _profile("steady")[0] if args.full else None
     if mfma and steady:
         def _rp_ms(kv):
             key = _family_key(steady, kv[0])
@@ -538,7 +581,7 @@ def main():
         mfma_families[k] = e
     step = None
     work = STEP_WORK.get((args.model, len(mods)))
-    if work is not None and args.size == 96 and args.dtype == "bf16":
+    if args.full and work is not None and args.size == 96 and args.dtype == "bf16":
         F, Bt = work[0] * args.batch, work[1] * args.batch
         t_mfma, t_hbm = F / (PEAK_BF16_TFLOPS * 1e12), Bt / (PEAK_HBM_GBS * 1e9)
         t_roof = max(t_mfma, t_hbm)
@@ -591,6 +634,7 @@ def main():
         "metric": f"{args.size}^3 {len(mods)}-modality patches/sec/node (train step)",
         "value": round(value, 3), "unit": "patches/s", "n_gpus": n_gpus, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
+        "full": args.full,
         "vs_baseline": None,
         "dtype": (args.dtype + ("+fp8" if args.fp8 else "")) if args.kernels == "hip"
         else f"{args.amp if args.dtype == 'bf16' else 'fp32'}-autocast",
@@ -609,7 +653,7 @@ def main():
         "cpu_baseline": cpu,
         "kernel_families": families,
         "mfma_families": mfma_families,
-        "profiles": {kind: _profile(kind)[1] for kind in ("steady", "pmc_traffic", "pmc_sq")},
+        "profiles": {kind: _profile(kind)[1] if args.full else None for kind in ("steady", "pmc_traffic", "pmc_sq")},
     }
     print(json.dumps(out), flush=True)
     if world > 1:

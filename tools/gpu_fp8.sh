@@ -9,7 +9,7 @@ rc=$?
 tail -2 $O/tests.log; grep "fp8 vs bf16" $O/tests.log
 [ $rc -ne 0 ] && { grep -E "^E |Error" $O/tests.log | head -8; exit $rc; }
 for f in "" "--fp8" "" "--fp8"; do
-  timeout -k 10 300 python3 $R/bench.py --modalities CT,PET,MRI --loss tversky --no-cpu-baseline --timer-steps 2 --steps 20 $f > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+  timeout -k 10 300 python3 $R/bench.py --full --modalities CT,PET,MRI --loss tversky --no-cpu-baseline --timer-steps 2 --steps 20 $f > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
   tail -1 $O/bench.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read())
 print('$f', d['dtype'], d['ms_per_step'], d['value'], d['loss'], {k: v['ms_per_step'] for k, v in d['kernel_families'].items() if 'brick6' in k or 'F8' in k})"

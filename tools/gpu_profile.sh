@@ -11,7 +11,7 @@ TAG=$1; CFG=$2; shift 2
 O=$R/gpurun_out/${TAG}_${CFG}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py $* --workload-out $O/workload.json"
+B="python3 $R/bench.py --full $* --workload-out $O/workload.json"
 STEPS="--steps ${PROF_STEPS:-10} --warmup 3 --timer-steps 1 --no-cpu-baseline"
 timeout -k 10 600 rocprofv3 -M --kernel-trace --stats --output-format csv -d $O/trace -o prof -- $B $STEPS > $O/prof.log 2>&1 || { echo "$CFG trace failed"; tail -20 $O/prof.log; exit 1; }
 echo "$CFG trace ok"

@@ -3,11 +3,12 @@ weight gradient of engine.swin.Lin, timed with HIP events; prints achieved GB/s 
 (A + out + weights).  --lib PATH times another build of the library (A/B runs in one GPU call).
     python tools/pointbench.py [--lib /path/libmmseg_hip.so] [--reps 20]"""
 import argparse
+import os
 import sys
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mmseg_amd  # noqa: F401,E402
 from mmseg_amd import _lib  # noqa: E402
 

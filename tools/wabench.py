@@ -3,11 +3,12 @@
 mmseg_winattn_bwd per stage with HIP events; run under rocprofv3 --kernel-trace --stats for the per-kernel split.
     python tools/wabench.py [--reps 20] [--stages 0,1] [--lib PATH]"""
 import argparse
+import os
 import sys
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mmseg_amd  # noqa: F401,E402
 from mmseg_amd._lib import lib, ptr, stream_handle  # noqa: E402
 
