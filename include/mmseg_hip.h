@@ -495,6 +495,17 @@ int mmseg_resize_nearest(const void* src, int label_bytes, int C, int D, int H, 
 int mmseg_phantom(int S, int ncls, const double* geo, int M, const float* class_mean, const float* noise_sd,
                   const int* abs_noise, const unsigned long long* keys, void* label, int label_bytes, float* image,
                   void* stream);
+/* Training augmentation of one sample in one launch (transforms.py:32-139: RandomFlip, RandomRotate90,
+ * RandomIntensityShift, RandomGaussianNoise with the draws already made on the host), out of place:
+ * src [C][D][H][W] fp32 (C <= 4) -> dst [C][D'][H'][W], label (int64 / uint8 by label_bytes; NULL = none)
+ * [D][H][W] -> label_dst alike, (D', H') = (H, D) for odd rot_k.  Geometry = np.flip on every axis whose bit
+ * is set in flip_mask (bit 0 D, bit 1 H, bit 2 W), then np.rot90(rot_k) over (D, H).  Then per element
+ * x * scale[c] + shift[c] in two float32 roundings (host arrays, both NULL = none), then, if noise,
+ * + (float)(noise_mean + noise_sd * N) with N element e (linear index into dst) of the SplitMix64
+ * counter stream *noise_key, as in mmseg_phantom. */
+int mmseg_augment(const float* src, int C, int D, int H, int W, const void* label, int label_bytes, int flip_mask,
+                  int rot_k, const float* scale, const float* shift, int noise, double noise_mean, float noise_sd,
+                  const unsigned long long* noise_key, float* dst, void* label_dst, void* stream);
 
 /* ------------------------------------------------ sliding-window inference */
 /* MONAI sliding_window_inference (constant blending) as called by Trainer._sliding_window_inference

@@ -17,6 +17,10 @@
 //   phantom             labels from host-drawn ellipsoids (fp64 tests in class
 //                       order), intensities = class mean + std * N with N from a
 //                       SplitMix64 counter stream through Box-Muller (fp64)
+//   augment             the training pipeline's random flip / rot90 / intensity
+//                       affine / Gaussian noise (transforms.py:32-139) of image and
+//                       label as one row-wise pass; draws made on the host
+//                       (data/augment.py), noise from the phantom's stream
 #include "mmseg_common.h"
 
 namespace {
@@ -225,6 +229,75 @@ __global__ void phantom_kernel(PhantomArgs a, L* __restrict__ label, float* __re
   }
 }
 
+// ----------------------------------------------------------------- augment
+// RandomFlip + RandomRotate90 + RandomIntensityShift + RandomGaussianNoise (transforms.py:32-139) as one pass.
+// np.flip on the masked axes followed by np.rot90(k) over (D, H) never permutes W, so output row (od, oh) is
+// input row (sd, sh) read forwards or backwards; the host folds flips and rotation into swap / rev_*.
+struct AugmentArgs {
+  int C, D, H, W;                    // source extents
+  int Do, Ho;                        // output extents of the rotated axes: (H, D) when k is odd
+  int swap, rev_d, rev_h, rev_w;     // (p, q) = swap ? (oh, od) : (od, oh); sd = rev_d ? D-1-p : p; sh likewise
+  int affine;
+  float scale[PH_MAXM], shift[PH_MAXM];
+  double mean;                       // noise = mean + sd * N(0, 1)
+  float sd;
+  uint64_t base;                     // splitmix64(key)
+};
+
+template <typename T, int VN>
+struct alignas(16) RowVec {
+  T v[VN];
+};
+
+// One row of W elements, d[x] = f(s[rev ? W-1-x : x], x), spread over the block's x threads: 16-byte vectors
+// while both the destination row and the source segment they read are 16-byte aligned, scalars for the tail
+// (and for the whole row when they are not).
+template <typename T, typename F>
+__device__ __forceinline__ void augment_row(const T* __restrict__ s, T* __restrict__ d, int W, bool rev, F&& f) {
+  constexpr int VN = 16 / (int)sizeof(T);
+  typedef RowVec<T, VN> Vec;
+  int nv = W / VN;
+  const T* sv = s + (rev ? W - nv * VN : 0);   // reversed: vector j of d comes from vector nv-1-j of this segment
+  if ((((uintptr_t)sv) | ((uintptr_t)d)) & 15) nv = 0;
+  for (int j = threadIdx.x; j < nv; j += blockDim.x) {
+    const Vec a = *reinterpret_cast<const Vec*>(sv + (rev ? nv - 1 - j : j) * VN);
+    Vec o;
+#pragma unroll
+    for (int i = 0; i < VN; ++i) o.v[i] = f(rev ? a.v[VN - 1 - i] : a.v[i], j * VN + i);
+    *reinterpret_cast<Vec*>(d + j * VN) = o;
+  }
+  for (int x = nv * VN + threadIdx.x; x < W; x += blockDim.x) d[x] = f(s[rev ? W - 1 - x : x], x);
+}
+
+// block (tx, ty): ty output rows per block, tx threads along each; blockIdx.y = channel, or C for the label.
+// NOISE is a template switch so that the common noise-free launch does not carry the fp64 Box-Muller registers.
+template <typename L, bool NOISE>
+__global__ void augment_kernel(AugmentArgs a, const float* __restrict__ src, const L* __restrict__ lsrc,
+                               float* __restrict__ dst, L* __restrict__ ldst) {
+  const int r = blockIdx.x * blockDim.y + threadIdx.y;
+  if (r >= a.Do * a.Ho) return;
+  const int od = r / a.Ho, oh = r - od * a.Ho;
+  const int p = a.swap ? oh : od, q = a.swap ? od : oh;
+  const int sd = a.rev_d ? a.D - 1 - p : p, sh = a.rev_h ? a.H - 1 - q : q;
+  const long long srow = ((long long)sd * a.H + sh) * a.W, drow = (long long)r * a.W;
+  const int c = blockIdx.y;
+  if (c == a.C) {
+    augment_row(lsrc + srow, ldst + drow, a.W, a.rev_w != 0, [](L v, int) { return v; });
+    return;
+  }
+  const long long plane = (long long)a.D * a.H * a.W;
+  const long long e0 = c * plane + drow;     // linear index into dst of this row's first element
+  const float sc = a.scale[c], sf = a.shift[c];
+  augment_row(src + c * plane + srow, dst + e0, a.W, a.rev_w != 0, [&](float v, int x) {
+    // two roundings, as numpy.  __fadd_rn(__fmul_rn()) would not do: the intrinsics are inline functions
+    // around a plain * and +, which the compiler contracts into one FMA after inlining
+#pragma clang fp contract(off)
+    if (a.affine) v = v * sc + sf;
+    if (NOISE) v = __fadd_rn(v, (float)(a.mean + (double)a.sd * normal_at(a.base, (uint64_t)(e0 + x))));
+    return v;
+  });
+}
+
 int grid_of(long long total) {
   long long b = (total + 255) / 256;
   return (int)(b < 8192 ? (b < 1 ? 1 : b) : 8192);
@@ -317,6 +390,53 @@ int mmseg_phantom(int S, int ncls, const double* geo, int M, const float* class_
   else
     MMSEG_LAUNCH(phantom_kernel<uint8_t>, dim3(grid_of(V)), dim3(256), 0, s, a, (uint8_t*)label, image);
   return mmseg::check_launch("phantom");
+}
+
+int mmseg_augment(const float* src, int C, int D, int H, int W, const void* label, int label_bytes, int flip_mask,
+                  int rot_k, const float* scale, const float* shift, int noise, double noise_mean, float noise_sd,
+                  const unsigned long long* noise_key, float* dst, void* label_dst, void* stream) {
+  MMSEG_REQUIRE(C >= 1 && C <= PH_MAXM, "augment: 1 <= channels <= %d (got %d)", PH_MAXM, C);
+  MMSEG_REQUIRE(D >= 1 && H >= 1 && W >= 1 && (long long)D * H <= 0x7fffffffLL, "augment: empty or oversized shape");
+  MMSEG_REQUIRE(rot_k >= 0 && rot_k <= 3, "augment: rot_k in 0..3 (got %d)", rot_k);
+  MMSEG_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "augment: flip_mask has one bit per spatial axis (got %d)", flip_mask);
+  MMSEG_REQUIRE(src != nullptr && dst != nullptr && src != dst, "augment: src and dst, out of place");
+  MMSEG_REQUIRE((scale == nullptr) == (shift == nullptr), "augment: scale and shift come together");
+  MMSEG_REQUIRE(!noise || noise_key != nullptr, "augment: noise needs a key");
+  if (label != nullptr) {
+    MMSEG_REQUIRE(label_bytes == 8 || label_bytes == 1, "augment: int64 or uint8 labels");
+    MMSEG_REQUIRE(label_dst != nullptr && label_dst != label, "augment: label_dst, out of place");
+  }
+  AugmentArgs a{};
+  a.C = C; a.D = D; a.H = H; a.W = W;
+  a.swap = rot_k & 1;
+  a.Do = a.swap ? H : D;
+  a.Ho = a.swap ? D : H;
+  // rot90 over (D, H): k=1 reads (oh, H-1-od), k=2 (D-1-od, H-1-oh), k=3 (D-1-oh, od); the flips act on the input
+  a.rev_d = (rot_k >= 2) ^ (flip_mask & 1);
+  a.rev_h = (rot_k == 1 || rot_k == 2) ^ ((flip_mask >> 1) & 1);
+  a.rev_w = (flip_mask >> 2) & 1;
+  a.affine = scale != nullptr;
+  for (int c = 0; c < C; ++c) {
+    a.scale[c] = scale ? scale[c] : 1.f;
+    a.shift[c] = shift ? shift[c] : 0.f;
+  }
+  a.mean = noise_mean;
+  a.sd = noise_sd;
+  a.base = noise ? splitmix64_host((uint64_t)*noise_key) : 0;
+  // threads along a row: one per 16-byte vector when rows can be vectors at all, else one per element
+  const int per_row = W % 4 == 0 ? W / 4 : W;
+  const int tx = per_row < 256 ? per_row : 256, ty = 256 / tx;
+  const dim3 block(tx, ty), grid(ceil_div((long long)a.Do * a.Ho, ty), C + (label != nullptr ? 1 : 0));
+  hipStream_t s = (hipStream_t)stream;
+#define AUG_LAUNCH(L, N) \
+  MMSEG_LAUNCH((augment_kernel<L, N>), grid, block, 0, s, a, src, (const L*)label, dst, (L*)label_dst)
+  if (label_bytes == 1 && label != nullptr) {
+    if (noise) AUG_LAUNCH(uint8_t, true); else AUG_LAUNCH(uint8_t, false);
+  } else {
+    if (noise) AUG_LAUNCH(int64_t, true); else AUG_LAUNCH(int64_t, false);
+  }
+#undef AUG_LAUNCH
+  return mmseg::check_launch("augment");
 }
 
 }  // extern "C"

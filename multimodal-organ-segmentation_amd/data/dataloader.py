@@ -4,7 +4,8 @@ The reference reads a CSV of NIfTI files (nibabel, absent here); the engine's
 loader serves the seeded synthetic phantoms of data/synthetic.py in the same
 batch format.  Under data parallelism each rank takes samples r, r+W, ...
 (DistributedSampler semantics).  With data.synthetic.device: true
-the phantoms are generated and normalised on the GPU instead (data/device.py)."""
+the phantoms are generated and normalised on the GPU instead (data/device.py), and
+data.augmentation.enabled: true augments the training split there (data/augment.py)."""
 from typing import Any, Dict
 
 import torch
@@ -27,18 +28,25 @@ def get_dataset(config: Dict[str, Any], split: str = "train"):
 
 def get_dataloader(config: Dict[str, Any], split: str = "train", shuffle=None, drop_last=None):
     syn = config["data"].get("synthetic") or {}
+    aug_cfg = config["data"].get("augmentation") or {}
+    augment = split == "train" and aug_cfg.get("enabled", False)    # get_transforms: the train pipeline only
     if syn.get("device", False):
         # data.synthetic.device: true -> phantoms generated and normalised on the GPU (data/device.py)
+        from .augment import DeviceAugment
         from .device import DeviceLoader, DevicePhantomDataset
         n = syn["n_train"] if split == "train" else syn.get("n_val", 2)
         seed = syn.get("seed", 1234) + (0 if split == "train" else 100000)
         ds = DevicePhantomDataset(n, syn.get("size", 96), config["model"]["out_channels"],
                                   config["data"]["modalities"], torch.device("cuda", torch.cuda.current_device()),
-                                  seed=seed, preprocessing=config["data"].get("preprocessing"))
+                                  seed=seed, preprocessing=config["data"].get("preprocessing"),
+                                  augment=DeviceAugment(aug_cfg) if augment else None)
         return DeviceLoader(ds, config["training"]["batch_size"],
                             shuffle=split == "train" if shuffle is None else shuffle,
                             drop_last=split == "train" if drop_last is None else drop_last, seed=seed,
                             pad=split == "train")
+    if augment:
+        raise NotImplementedError("data.augmentation.enabled needs the device data path: set "
+                                  "data.synthetic.device: true (augmentation is a HIP pass, there is no CPU path)")
     ds = get_dataset(config, split)
     w, r = ddp.world(), ddp.rank()
     if w > 1:   # training shards are padded to equal length, validation shards are not (each sample once)

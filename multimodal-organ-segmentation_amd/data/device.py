@@ -145,20 +145,28 @@ class DevicePhantomDataset:
     on the GPU, in the reference's batch format."""
 
     def __init__(self, n: int, size: int, num_classes: int, modalities: Sequence[str], device,
-                 seed: int = 1234, preprocessing: Optional[Dict] = None, resize=None):
+                 seed: int = 1234, preprocessing: Optional[Dict] = None, resize=None, augment=None):
         self.n, self.size, self.C, self.mods, self.seed = n, size, num_classes, list(modalities), seed
         self.device = torch.device(device)
         self.norm = DeviceModalityNormalize({"data": {"modalities": self.mods,
                                                       "preprocessing": preprocessing or DEFAULT_PREPROCESSING}})
         self.resize = DeviceResize(resize) if resize is not None else None
+        self.augment = augment     # a DeviceAugment (data/augment.py): training only
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i: int) -> Dict[str, Any]:
+        return self.get(i, 0)
+
+    def get(self, i: int, epoch: int) -> Dict[str, Any]:
+        """Sample i as epoch `epoch` sees it: normalise, augment, resize (the reference's order,
+        transforms.py:418-451).  Without augmentation the epoch changes nothing."""
         image, label = device_phantom(self.seed + i, self.size, self.C, self.mods, self.device)
         self.norm(image)
         sample = {"image": image, "label": label}
+        if self.augment is not None:
+            sample = self.augment(sample, epoch, i, self.seed)
         if self.resize is not None:
             sample = self.resize(sample)
         sample["patient_id"] = f"synthetic_{self.seed + i}"
@@ -187,9 +195,10 @@ class DeviceLoader:
         if self.shuffle:
             rng = np.random.Generator(np.random.PCG64(self.seed + self.epoch))
             order = [order[k] for k in rng.permutation(len(order))]
+        epoch = self.epoch
         self.epoch += 1
         for b in range(len(self)):
-            items = [self.ds[i] for i in order[b * self.B:(b + 1) * self.B]]
+            items = [self.ds.get(i, epoch) for i in order[b * self.B:(b + 1) * self.B]]
             batch = {"image": torch.stack([it["image"] for it in items]),
                      "label": torch.stack([it["label"] for it in items]),
                      "patient_id": [it["patient_id"] for it in items]}
