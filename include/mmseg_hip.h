@@ -76,7 +76,7 @@ int mmseg_pack_weights_batched(const void* descs, int n, long long total, int dt
 /* CONV3 data gradient (ksplit 1, no bias) that also writes the InstanceNorm-backward partial sums of its output:
  * the output is dy of an InstanceNorm + ReLU with pre-norm input inx (pitch ldinx) and statistics inmean /
  * inrstd [N][Ncols]; inpart [N][mmseg_conv3_dgrad_in_chunks()][Ncols][2] = (sum g, sum g xhat), g = dy [xhat > 0],
- * the layout mmseg_instnorm_bwd_part reads.  bf16, the brick5 kernel's shapes only (chunks 0 otherwise). */
+ * the layout mmseg_instnorm_bwd_part reads.  bf16, the brick6 kernel's shapes only (chunks 0 otherwise). */
 int mmseg_conv3_dgrad_in_chunks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
                                 int ldo, int dtype);
 int mmseg_conv3_dgrad_in(const void* a, int lda, const void* wpacked, void* out, int ldo, int M, int Ncols, int Cpad,
@@ -105,12 +105,6 @@ int mmseg_stem_kp(int cr);
 int mmseg_stem_wgrad_splits(int N, int D, int H, int W, int want);
 int mmseg_stem_fwd(const void* x, int ldx, int cr, const float* w, const float* bias, void* y, int ldy, int N, int D,
                    int H, int W, int Co, int dtype, void* stream);
-/* mmseg_stem_fwd that also writes InstanceNorm partials of its output: stats [N][mmseg_stem_stats_bricks()][Co][2]
- * = (mean, M2) of the stored values over each 1x8x8 slice of its 4x8x8 bricks (64 voxels), the input of
- * mmseg_instnorm_stats_bricks(stats, N, Co, slices, 64, ...). */
-int mmseg_stem_stats_bricks(int D, int H, int W);
-int mmseg_stem_fwd_stats(const void* x, int ldx, int cr, const float* w, const float* bias, void* y, int ldy, int N,
-                         int D, int H, int W, int Co, float* stats, int dtype, void* stream);
 int mmseg_stem_wgrad(const void* dy, int lddy, const void* x, int ldx, int cr, float* part, float* bias_part, int N,
                      int D, int H, int W, int Co, int ksplit, int dtype, void* stream);
 /* mmseg_stem_wgrad whose dy is the gradient of an InstanceNorm + ReLU OUTPUT: the norm's backward (pre-norm
@@ -121,30 +115,16 @@ int mmseg_stem_wgrad_inb(const void* dy, int lddy, const void* x, int ldx, int c
                          const float* inmean, const float* inrstd, const float* incoef, float* part, float* bias_part,
                          int N, int D, int H, int W, int Co, int ksplit, int dtype, void* stream);
 
-/* Fused InstanceNorm statistics (unet.py:34 InstanceNorm3d following each Conv3d): when the CONV3 brick kernel
- * for a shape can emit them, mmseg_conv3_stats_bricks returns the bricks per sample (value-returning, 0 = not
- * available) and mmseg_conv_gemm_stats writes stats_part[N][bricks][Ncols][2] = per-brick (mean, M2) of the stored
- * outputs; mmseg_instnorm_stats_bricks turns them into mean / rstd, replacing the statistics pass over the output. */
-int mmseg_conv3_stats_bricks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
-                             int dtype);
-int mmseg_conv_gemm_stats(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                          float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
-                          int W, int ksplit, float* stats_part, int dtype, void* stream);
-/* mmseg_conv_gemm_stats whose A source holds only cin_real real channels (the rest are channel padding with zero
- * packed weights, e.g. SwinUNETR's 96 / 192 / 384 / 768-channel tensors stored as 128 / 256 / 512 / 1024): the CONV3
- * brick kernels skip the 32-channel K chunks wholly past cin_real.  cin_real = 0: all channels are real.  Replaces
- * the same Conv3d call sites as mmseg_conv_gemm (monai SwinUNETR's UnetResBlock convs). */
-int mmseg_conv_gemm_ex(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                       float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
-                       int W, int ksplit, float* stats_part, int cin_real, int dtype, void* stream);
-/* mmseg_conv_gemm_ex (no statistics) with a whole-row output hint: the brick2 conv kernels also write zeros into
- * columns [Ncols, zcols) of the output rows (zcols <= min(ldo, Ncols + 48), multiple of 8; 0 = none), so 48 / 96
- * real columns at pitch 64 / 128 are written in whole 128-B lines; other kernels leave those columns alone. */
+/* mmseg_conv_gemm whose A source holds only cin_real real channels (the rest are channel padding with zero packed
+ * weights, e.g. SwinUNETR's 96 / 192 / 384 / 768-channel tensors stored as 128 / 256 / 512 / 1024): the CONV3 brick
+ * kernels skip the 32-channel K chunks wholly past cin_real.  cin_real = 0: all channels are real.  Replaces the same
+ * Conv3d call sites as mmseg_conv_gemm (monai SwinUNETR's UnetResBlock convs).
+ * Whole-row output hint: the brick2 conv kernels also write zeros into columns [Ncols, zcols) of the output rows
+ * (zcols <= min(ldo, Ncols + 48), multiple of 8; 0 = none), so 48 / 96 real columns at pitch 64 / 128 are written in
+ * whole 128-B lines; other kernels leave those columns alone. */
 int mmseg_conv_gemm_zw(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
                        float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
                        int W, int ksplit, int cin_real, int zcols, int dtype, void* stream);
-int mmseg_instnorm_stats_bricks(const float* part, int N, int C, int nb, int cnt, float eps, float* mean, int mean_ld,
-                                float* rstd, void* stream);
 
 /* Weight-gradient partials part[ksplit][Ca][Ncols] (fp32), K = voxels.
  * Replaces convolution_backward (grad_weight) of the same layers; with
@@ -169,7 +149,7 @@ long long mmseg_conv3_wgrad_ws_floats(long long V, int Co, int Cip, int Ci, int 
 int mmseg_conv3_wgrad(const void* dy, int lddy, const void* x, int ldx, float* grad, float* bias_grad, int Co, int Cip,
                       int Ci, int cpg_shift, long long V, int D, int H, int W, float* ws, long long ws_floats,
                       int accumulate, int dtype, void* stream);
-/* mmseg_conv_gemm_ex (without fused statistics) with the output columns [split, Ncols) written to a second
+/* mmseg_conv_gemm (cin_real as mmseg_conv_gemm_zw) with the output columns [split, Ncols) written to a second
  * tensor out2 (row pitch ldo2) as its columns 0..Ncols-split-1 (split, ldo, ldo2 multiples of 8, out2 16-B
  * aligned; not the transposed-conv forward): the decoder's first-conv data gradient writes d(upsampled) and
  * d(skip) as two dense tensors. */
@@ -193,7 +173,7 @@ int mmseg_conv_gemm_gelu(const void* a, int lda, const void* wpacked, const floa
 /* Deferred InstanceNorm + ReLU of a 3^3 conv's input (the block's conv1 output is never written by its
  * normalisation pass): the input holds the PRE-norm activation and the kernels stage
  * relu((x - mean[n][c]) * rstd[n][c]) rounded to bf16, the values mmseg_instnorm_relu_fwd would write.
- * *_ok return 1 when the shape runs the kernels that support it (brick5 forward, brick2 weight gradient). */
+ * *_ok return 1 when the shape runs the kernels that support it (brick6 forward, brick2 weight gradient). */
 int mmseg_conv3_norm_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                         int dtype);
 int mmseg_conv3_fwd_norm(const void* a, int lda, const float* nmean, const float* nrstd, const void* wpacked,
@@ -217,7 +197,7 @@ int mmseg_conv3_wgrad_norm(const void* dy, int lddy, const void* x, int ldx, con
                            int H, int W, float* ws, long long ws_floats, int accumulate, int dtype, void* stream);
 /* Grouped forms for `groups` same-shape layers over equal sample groups of one activation tensor (group gi:
  * samples [gi N / groups, (gi + 1) N / groups)), each with its own weights: the M modality encoders' small levels
- * (12^3 / 6^3, runtime-brick kernels) as one launch instead of M.  Replace the same ATen ops as mmseg_conv_gemm_ex /
+ * (12^3 / 6^3, runtime-brick kernels) as one launch instead of M.  Replace the same ATen ops as mmseg_conv_gemm /
  * mmseg_conv3_wgrad (reference unet.py:26-27, run once per modality encoder, dual_encoder.py:112-165).
  * conv_gemm_group: group gi reads wpacked + gi * w_gstride (elements) and bias + gi * b_gstride.
  * conv3_wgrad_group: group gi's gradients go to grad + gi * grad_gstride / bias_grad + gi * bias_gstride floats;
@@ -232,15 +212,6 @@ int mmseg_conv3_wgrad_group_ok(long long V, int Co, int Cip, int Ci, int cpg_shi
                                int ldx, int dtype);
 int mmseg_conv3_group_splits(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                              int dtype);
-/* conv_gemm_group + the output's per-brick InstanceNorm partials (the runtime-brick epilogue; one split): stats_part
- * [M / (D H W)][conv3_group_stats_bricks()][Ncols][2] (mean, M2), merged by mmseg_instnorm_stats_bricks -- the
- * grouped 48^3 / 24^3 levels' statistics without a pass over the output (reference unet.py:28-29 InstanceNorm). */
-int mmseg_conv3_group_stats_bricks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
-                                   int ldo, int dtype);
-int mmseg_conv_gemm_group_stats(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                                int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W,
-                                int cin_real, int groups, long long w_gstride, int b_gstride, float* stats_part,
-                                int dtype, void* stream);
 long long mmseg_conv3_wgrad_group_ws_floats(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W,
                                             int lddy, int ldx, int groups, int dtype);
 int mmseg_conv3_wgrad_group(const void* dy, int lddy, const void* x, int ldx, float* grad, float* bias_grad, int Co,

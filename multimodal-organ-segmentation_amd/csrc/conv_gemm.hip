@@ -83,10 +83,9 @@ struct GemmArgs {
   int D, H, W;               // row grid
   int ksplit, kg_per_split;  // k-groups per split (multiple of 4)
   int swz;                   // XCD-aware block remap
-  float* stats;              // brick kernels, ksplit == 1: per-brick InstanceNorm partials (mean, M2), or null
   int kchunks;               // CONV3 brick kernels: 32-channel input chunks holding real channels (0 = all);
                              // the packed weights of the rest are zero (channel-padded K side), so they are skipped
-  // deferred InstanceNorm + ReLU of the A source (brick5 only, mmseg_conv3_fwd_norm): A holds the PRE-norm
+  // deferred InstanceNorm + ReLU of the A source (brick6 only, mmseg_conv3_fwd_norm): A holds the PRE-norm
   // activation, the kernel stages relu((a - nmean[n][c]) * nrstd[n][c]) rounded to T (in_relu_apply's values)
   const float* nmean;
   const float* nrstd;
@@ -95,7 +94,7 @@ struct GemmArgs {
   // [voxel][2F] tensor whose halves every later reader fetched at half a cache line per voxel.
   void* out2;
   int ldo2, split;
-  // InstanceNorm-backward partials of the output (brick5 data gradient only, mmseg_conv3_dgrad_in): the output is
+  // InstanceNorm-backward partials of the output (brick6 data gradient only, mmseg_conv3_dgrad_in): the output is
   // the gradient dy of an InstanceNorm + ReLU whose PRE-norm input is inx (pitch ldinx, statistics inmean /
   // inrstd [N][Ncols]); the kernel also writes inpart[n][block][col][2] = (sum g, sum g xhat), g = dy [xhat > 0]
   const void* inx;
@@ -103,7 +102,6 @@ struct GemmArgs {
   const float* inmean;
   const float* inrstd;
   float* inpart;
-  int prio;   // (unused: the s_setprio experiments of round 3 measured +-2 % and were removed)
   // fp8 forward (brick6 F8, mmseg_conv3_fwd_fp8): b holds e4m3 weights w * s[co] (s = 448 / max |w[co]|), wdq[co] =
   // 1 / s[co] restores the scale in the epilogue; the staged activations are e4m3 at unit scale
   const float* wdq;
@@ -152,45 +150,6 @@ __device__ __forceinline__ void norm_relu8(V8<T>& v, const float* mu, const floa
 __host__ __device__ __forceinline__ int gemm_nchunk(const GemmArgs& g) {
   const int n = (8 << g.cpg_shift) / 32;
   return (g.kchunks > 0 && g.kchunks < n) ? g.kchunks : n;
-}
-
-// Per-brick InstanceNorm statistics of a staged output tile (fused into the
-// brick conv epilogue, so the IN stats pass never re-reads the conv output).
-// El: [rows][EP] staged outputs (already rounded to the storage type, i.e. the
-// exact values InstanceNorm will read); channel c = tid % BN, voxel slices
-// tid / BN.  Two passes over LDS (mean, then sum of squared deviations), fixed
-// order -> deterministic.  out[(brick * C + col) * 2 + {0, 1}] = (mean, M2).
-template <typename T, int BN>
-__device__ __forceinline__ void brick_in_stats(const T* El, int EP, int rows, float* red, float* out, long long brick,
-                                               int n0, int C) {
-  constexpr int S = 256 / BN;
-  const int tid = threadIdx.x, c = tid % BN, sl = tid / BN;
-  float a = 0.f;
-  for (int v = sl; v < rows; v += S) a += (float)El[v * EP + c];
-  red[tid] = a;
-  __syncthreads();
-  if (tid < BN) {
-    float t = 0.f;
-    for (int k = 0; k < S; ++k) t += red[k * BN + tid];
-    red[256 + tid] = t / (float)rows;
-  }
-  __syncthreads();
-  const float mu = red[256 + c];
-  float q = 0.f;
-  for (int v = sl; v < rows; v += S) {
-    const float d = (float)El[v * EP + c] - mu;
-    q = fmaf(d, d, q);
-  }
-  __syncthreads();
-  red[tid] = q;
-  __syncthreads();
-  if (tid < BN && n0 + tid < C) {
-    float t = 0.f;
-    for (int k = 0; k < S; ++k) t += red[k * BN + tid];
-    float* o = out + (brick * C + n0 + tid) * 2;
-    o[0] = red[256 + tid];
-    o[1] = t;
-  }
 }
 
 template <typename T>
@@ -852,7 +811,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void conv3_brick2_kern
   // epilogue: acc (+bias) -> LDS tile [BZ*64 voxels][BN] -> 16-B vector stores
   T* El = reinterpret_cast<T*>(lds4);
   constexpr int EP = BN + 8;   // padded pitch (elements)
-  static_assert(BZ * 64 * (BN + 8) * sizeof(T) + 2048 <= LQ * 16, "epilogue tile (+ stats scratch) must fit");
+  static_assert(BZ * 64 * (BN + 8) * sizeof(T) <= LQ * 16, "epilogue tile must fit");
 #pragma unroll
   for (int j = 0; j < RN; ++j) {
     const int col = j * 16 + r16;
@@ -866,11 +825,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void conv3_brick2_kern
       }
   }
   __syncthreads();
-  if (g.stats) {
-    float* red = reinterpret_cast<float*>(El + BZ * 64 * EP);
-    const long long brick = (long long)n * (bz_n * by_n * bx_n) + ((long long)bz * by_n + by) * bx_n + bx;
-    brick_in_stats<T, BN>(El, EP, BZ * 64, red, g.stats, brick, n0, g.Ncols);
-  }
   T* O = reinterpret_cast<T*>(g.out);
   constexpr int CG = BN / 8;                  // 8-column groups per voxel
   constexpr int O_ITEMS = BZ * 64 * CG;
@@ -1165,7 +1119,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void conv3_brick3_kern
 // Measured (s_memtime stamps, 96^3 B=2 forward): ~200 cycles per tap against 128 of MFMA issue, and the
 // tap loop speeds up in proportion when the per-tap A reads are cut (half the reads: 146 cycles per tap):
 // the LDS read stream, not latency, barriers or the halo loads, is what bounds this kernel.
-// Requirements (host): bf16, one 32-channel K chunk, Ncols % 32 == 0, D % 4, H % 8, W % 8, no fused stats.
+// Requirements (host): bf16, one 32-channel K chunk, Ncols % 32 == 0, D % 4, H % 8, W % 8.
 
 // MFMA with the weight fragment pinned to the accumulator file: hipcc otherwise keeps the 216 weight
 // registers in VGPRs and, short of VGPRs, issues each tap's LDS reads just before their MFMAs.  The asm is one
@@ -1349,398 +1303,33 @@ __global__ __launch_bounds__(256, 1) void conv3_brick4_kernel(GemmArgs g, int up
   }
 }
 
-// ------------------------------------------------- brick conv v5 (3^3, bf16, Cin = 32, Co tile 32)
+// ------------------------------------------------- brick conv v6 (3^3, bf16, Cin = 32, Co tile 32)
 // brick4 with the A-read stream halved.  A row tile is 16 consecutive x voxels of ONE y row (brick 4 z x
 // 4 y x 16 x, one z plane per wave), so the fragment of row tile i at tap ky is the fragment of halo row
 // i + ky: per (kz, kx) the 12 (ky, i) fragments are 6 distinct halo rows, read once and used by 24 MFMAs
 // (0.25 ds_read_b128 per MFMA instead of 0.5).  Halo image: voxel = 4 quads of 8 channels, the quad of
 // channel group kg at slot kg ^ (((hx >> 2) & 1) << 1), which makes the 16-lane groups of ds_read_b128
 // conflict-free for all three kx shifts; rows of 18 voxels, no padding.
-// Requirements (host): bf16, one 32-channel K chunk, Ncols % 32 == 0, D % 4, H % 4, W % 16, no fused stats.
-// INP (with DMA: the halo staging registers are free for it): the epilogue also sums the InstanceNorm-backward
-// partials of its output (GemmArgs::inpart); x of the brick is loaded during the brick's MFMA groups 4..5.
-template <bool DBG = false, bool DMA = false, bool INP = false>
-__global__ __launch_bounds__(256, 1) void conv3_brick5_kernel(GemmArgs g, int upb, int blocks_per_nt,
-                                                              long long* dbg = nullptr) {
-  using T = bf16_t;
-  constexpr int BZ = 4, BY = 4, BX = 16;
-  constexpr int HZ = BZ + 2, HY = BY + 2, HX = BX + 2;
-  constexpr int RY = HX * 4, RZ = HY * RY;             // quads per halo row / plane
-  constexpr int XQ = HZ * RZ;                          // 2592 quads = 41.5 KB
-  constexpr int RN = 2;
-  constexpr int XROWS = HZ * HY;                       // 36 (z, y) halo rows
-  constexpr int XK = XROWS / 3;                        // rows per thread (3 rows per pass of 216 threads)
-  __shared__ __attribute__((aligned(16))) float4 lds4[2 * XQ];
-  T* Xl = reinterpret_cast<T*>(lds4);
-  constexpr int EPQ = 8;
-
-  const T* Bw = reinterpret_cast<const T*>(g.b);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int bz_n = g.D / BZ, by_n = g.H / BY, bx_n = g.W / BX;
-  const int nbrick = (g.M / (g.D * g.H * g.W)) * bz_n * by_n * bx_n;
-  const int blk_all = g.swz ? xcd_swizzle(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int nt = blk_all / blocks_per_nt, blk = blk_all - nt * blocks_per_nt;
-  const int n0 = nt * 32;
-  const int u_begin = blk * upb;
-  const int u_end = u_begin + upb < nbrick ? u_begin + upb : nbrick;
-  if (u_begin >= u_end || n0 >= g.Ncols) return;
-  const int HW = g.H * g.W;
-  const int cin = 8 << g.cpg_shift;
-  const int ldb = g.lda * (int)sizeof(T);
-  const int vox_per_n = g.D * HW;
-  const int r16 = lane & 15, kg = lane >> 4;
-  // timing probe (DBG): lane 0 of waves 0 / 3 of blocks 0 and 100 record (s_memtime, s_memrealtime) pairs
-  long long* dp = nullptr;
-  int dn = 0;
-  if constexpr (DBG) {
-    const int sl = (blockIdx.x == 0 ? 0 : blockIdx.x == 100 ? 2 : -9) + (tid == 0 ? 0 : tid == 192 ? 1 : -9);
-    if (sl >= 0) dp = dbg + sl * 128;
-  }
-  auto stamp = [&]() {
-    if constexpr (DBG) {
-      if (dp && dn < 64) {
-        dp[64 + dn] = (long long)__builtin_amdgcn_s_memrealtime();
-        dp[dn++] = (long long)__builtin_amdgcn_s_memtime();
-      }
-    }
-  };
-  stamp();
-
-  V8<T> wf[27][RN];
-#pragma unroll
-  for (int t = 0; t < 27; ++t)
-#pragma unroll
-    for (int j = 0; j < RN; ++j)
-      wf[t][j].load(Bw + ((long long)(t * (cin / 8) + kg) * g.Cpad + n0 + 8 * (r16 >> 2) + 4 * j + (r16 & 3)) * 8);
-#pragma unroll
-  for (int t = 0; t < 27; ++t) brick4_wfence(wf[t][0].v, wf[t][1].v);
-
-  // ---- halo staging: thread t < 216 owns quad column (hx, cg) = divmod(t % 72, 4) of rows t / 72 + 3k
-  const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(g.a), 0, (int)((long long)(g.M / vox_per_n) * vox_per_n * ldb), 0x00020000);
-  const bool xact = tid < 216;
-  const int xq = tid % 72, r0 = tid / 72;
-  const int hx = xq >> 2, cg = xq & 3;
-  const int xlds0 = (hx * 4 + (cg ^ (((hx >> 2) & 1) << 1))) * EPQ;
-  struct Unit { int n, z0, y0, x0; };
-  auto unit_of = [&](int b) {
-    Unit r;
-    const int bx = b % bx_n; b /= bx_n;
-    const int by = b % by_n; b /= by_n;
-    r.z0 = (b % bz_n) * BZ;
-    r.n = b / bz_n;
-    r.y0 = by * BY;
-    r.x0 = bx * BX;
-    return r;
-  };
-  V8<T> xr[XK];
-  // byte offset of row k's element relative to the halo origin (z0 - 1, y0 - 1, x0 - 1), fixed per thread
-  uint32_t rel[XK];
-#pragma unroll
-  for (int k = 0; k < XK; ++k) {
-    const int row = r0 + 3 * k, hz = row / HY, hy = row - hz * HY;
-    rel[k] = (uint32_t)((hz * HW + hy * g.W + hx) * ldb + cg * 16);
-  }
-  // halo offsets of a brick: z / y interior bricks need one x test per lane (the unit base is uniform);
-  // border bricks test every row.  Out-of-volume lanes point past the buffer end and read zeros.
-  uint32_t xo[XK];
-  // deferred norm of the A source: the statistics of the sample of the brick being staged (set_x runs once per
-  // staged brick, before its store_x)
-  float nmu[8], nrs[8];
-  int norm_n = -1;
-  auto set_x = [&](const Unit& q) {
-    if (g.nmean && q.n != norm_n) {
-      norm_n = q.n;
-      const int cb = q.n * cin + cg * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        nmu[j] = g.nmean[cb + j];
-        nrs[j] = g.nrstd[cb + j];
-      }
-    }
-    const int xx = q.x0 - 1 + hx;
-    const bool xok = xact && (unsigned)xx < (unsigned)g.W;
-    const int ob = ((q.n * g.D + q.z0 - 1) * g.H + q.y0 - 1) * g.W + q.x0 - 1;   // origin voxel (may be -1)
-    const uint32_t base = (uint32_t)(ob * ldb);
-    if (q.z0 >= 1 && q.z0 + BZ < g.D && q.y0 >= 1 && q.y0 + BY < g.H) {
-#pragma unroll
-      for (int k = 0; k < XK; ++k) xo[k] = xok ? base + rel[k] : 0x80000000u;
-    } else {
-#pragma unroll
-      for (int k = 0; k < XK; ++k) {
-        const int row = r0 + 3 * k, hz = row / HY, hy = row - hz * HY;
-        const int zz = q.z0 - 1 + hz, yy = q.y0 - 1 + hy;
-        const bool ok = xok && (unsigned)zz < (unsigned)g.D && (unsigned)yy < (unsigned)g.H;
-        xo[k] = ok ? base + rel[k] : 0x80000000u;
-      }
-    }
-  };
-  auto load_x = [&](int k0, int k1) {
-#pragma unroll
-    for (int k = k0; k < k1; ++k) buf_load_v8<T>(xr[k], arsrc, xo[k]);
-  };
-  // DMA: the halo goes straight from HBM into the LDS image (buffer_load ... lds; no staging registers, no
-  // ds_write).  Wave-instruction m covers image quads [64 m, 64 m + 64); wave w issues m = w, w + 4, ...
-  constexpr int DM = (XQ + 63) / 64;                  // 41 wave-instructions per halo
-  constexpr int DK = (DM + 3) / 4;                    // per wave (the last ones partly or wholly empty)
-  uint32_t drel[DK];                                  // lane's byte offset from the halo origin, or ~0u (no quad)
-  uint32_t dlm = 0, drm = 0;                          // bit k: lane's quad k is in halo column hx = 0 / hx = 17
-#pragma unroll
-  for (int kk = 0; kk < DK; ++kk) {
-    const int p = (wave + 4 * kk) * 64 + lane;
-    const int row = p / RY, qi = p - row * RY, h = qi >> 2, sl = qi & 3;
-    const int c = sl ^ (((h >> 2) & 1) << 1);
-    const int hz = row / HY, hy = row - hz * HY;
-    drel[kk] = p < XQ ? (uint32_t)((hz * HW + hy * g.W + h) * ldb + c * 16) : ~0u;
-    if (h == 0) dlm |= 1u << kk;
-    if (h == HX - 1) drm |= 1u << kk;
-  }
-  uint32_t dof[DK];
-  auto set_xd = [&](const Unit& q) {
-    const int ob = ((q.n * g.D + q.z0 - 1) * g.H + q.y0 - 1) * g.W + q.x0 - 1;
-    const uint32_t base = (uint32_t)(ob * ldb);
-    const uint32_t xbad = (q.x0 == 0 ? dlm : 0u) | (q.x0 + BX == g.W ? drm : 0u);
-    const bool inner = q.z0 >= 1 && q.z0 + BZ < g.D && q.y0 >= 1 && q.y0 + BY < g.H;
-#pragma unroll
-    for (int kk = 0; kk < DK; ++kk) {
-      bool ok = drel[kk] != ~0u && !((xbad >> kk) & 1u);
-      if (!inner) {
-        const int p = (wave + 4 * kk) * 64 + lane;
-        const int row = p / RY, hz = row / HY, hy = row - hz * HY;
-        ok = ok && (unsigned)(q.z0 - 1 + hz) < (unsigned)g.D && (unsigned)(q.y0 - 1 + hy) < (unsigned)g.H;
-      }
-      dof[kk] = ok ? base + drel[kk] : 0x80000000u;
-    }
-  };
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  auto issue_xd = [&](int buf, int k0, int k1) {
-#pragma unroll
-    for (int kk = k0; kk < k1; ++kk) {
-      if (wave + 4 * kk < DM)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            arsrc, (lds_ptr_t)(lds4 + buf * XQ + (wave + 4 * kk) * 64), 16, dof[kk], 0, 0, 0);
-    }
-  };
-  auto store_x = [&](int buf, int k0, int k1) {
-    if (xact) {
-#pragma unroll
-      for (int k = k0; k < k1; ++k) {
-        if (g.nmean && xo[k] != 0x80000000u) norm_relu8<T>(xr[k], nmu, nrs);   // padding stays 0
-        xr[k].store(Xl + (buf * XQ + (r0 + 3 * k) * RY) * EPQ + xlds0);
-      }
-    }
-  };
-  // per-lane A offsets (quads) of the three kx shifts: voxel hx = r16 + kx, channel group kg
-  int ao[3];
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) {
-    const int h = r16 + kx;
-    ao[kx] = wave * RZ + h * 4 + (kg ^ (((h >> 2) & 1) << 1));
-  }
-  float bv[RN][4];
-#pragma unroll
-  for (int j = 0; j < RN; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bv[j][r] = g.bias ? g.bias[n0 + 8 * kg + 4 * j + r] : 0.f;
-  T* O = reinterpret_cast<T*>(g.out);
-
-  // InstanceNorm-backward partials (INP): per lane the sums over its voxels of g and g (x - mean) for its 8
-  // channels n0 + 8 kg + (0..7) (times rstd at the flush), g = dy if x > mean (xhat > 0; rstd > 0) else 0
-  float isg[8], isgx[8], imu[8];
-  int in_n = -1;
-  V8<T> xin[BY];
-  __shared__ float ired[INP ? 4 : 1][2][32];
-  if constexpr (INP) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) isg[k] = isgx[k] = 0.f;
-  }
-  // block-wide: the sums of sample in_n -> inpart[in_n][blk][n0 + c] (fixed order: 16-lane tree, then waves 0..3)
-  auto in_flush = [&]() {
-   if constexpr (INP) {   // (the 1-wave LDS array of the plain instantiations is never read)
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        isg[k] += __shfl_xor(isg[k], o, 64);
-        isgx[k] += __shfl_xor(isgx[k], o, 64);
-      }
-    if (r16 == 0)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        ired[wave][0][8 * kg + k] = isg[k];
-        ired[wave][1][8 * kg + k] = isgx[k];
-      }
-    __syncthreads();
-    if (tid < 32) {
-      const float a = ired[0][0][tid] + ired[1][0][tid] + ired[2][0][tid] + ired[3][0][tid];
-      const float c = ired[0][1][tid] + ired[1][1][tid] + ired[2][1][tid] + ired[3][1][tid];
-      float* p = g.inpart + (((long long)in_n * blocks_per_nt + blk) * g.Ncols + n0 + tid) * 2;
-      p[0] = a;
-      p[1] = c * g.inrstd[in_n * g.Ncols + n0 + tid];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) isg[k] = isgx[k] = 0.f;
-   }
-  };
-  auto in_load = [&](const Unit& q) {   // x of the lane's 4 output voxels (consumed by the brick's epilogue)
-    const T* X = reinterpret_cast<const T*>(g.inx) + (long long)q.n * vox_per_n * g.ldinx + n0 + 8 * kg;
-#pragma unroll
-    for (int i = 0; i < BY; ++i)
-      xin[i].load(X + (long long)((q.z0 + wave) * g.H + q.y0 + i) * g.W * g.ldinx +
-                  (long long)(q.x0 + r16) * g.ldinx);
-  };
-
-  // epilogue of a finished brick (ev = its accumulators, copied out of the AGPRs): lane holds channels
-  // n0 + 8*kg + 4*j + (0..3) of voxel (z0 + wave, y0 + i, x0 + r16): one 16-B store per row tile
-  f32x4 ev[BY][RN];
-  auto epilogue = [&](const Unit& q) {
-    const long long obase = (long long)q.n * vox_per_n;
-    if constexpr (INP) {
-      if (q.n != in_n) {   // block-uniform
-        if (in_n >= 0) in_flush();
-        in_n = q.n;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) imu[k] = g.inmean[in_n * g.Ncols + n0 + 8 * kg + k];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < BY; ++i) {
-      const int z = q.z0 + wave, y = q.y0 + i, x = q.x0 + r16;
-      T* dst = out_at<T>(g, obase + (long long)(z * g.H + y) * g.W + x, n0 + 8 * kg);
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < RN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[4 * j + r] = (bf16_t)(ev[i][j][r] + bv[j][r]);
-      *reinterpret_cast<bf16x8*>(dst) = o;
-      if constexpr (INP) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float d = xin[i].get(k) - imu[k];
-          const float gg = d > 0.f ? (float)o[k] : 0.f;
-          isg[k] += gg;
-          isgx[k] = fmaf(gg, d, isgx[k]);
-        }
-      }
-    }
-  };
-  Unit cur = unit_of(u_begin), prev = cur;
-  if constexpr (DMA) {
-    set_xd(cur);
-    issue_xd(0, 0, DK);
-    __builtin_amdgcn_s_waitcnt(0x0f70);    // vmcnt(0): this wave's halo pieces have landed
-  } else {
-    set_x(cur);
-    load_x(0, XK);
-    store_x(0, 0, XK);
-  }
-  __syncthreads();
-  stamp();
-  int b = 0;
-  for (int u = u_begin; u < u_end; ++u) {
-    f32x4 acc[BY][RN];
-#pragma unroll
-    for (int i = 0; i < BY; ++i)
-#pragma unroll
-      for (int j = 0; j < RN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const bool unext = u + 1 < u_end;
-    Unit nxt = cur;
-    if (unext) {
-      // next brick of the contiguous range (x fastest), stepped with uniform adds instead of divisions
-      nxt.x0 += BX;
-      if (nxt.x0 == g.W) {
-        nxt.x0 = 0;
-        nxt.y0 += BY;
-        if (nxt.y0 == g.H) {
-          nxt.y0 = 0;
-          nxt.z0 += BZ;
-          if (nxt.z0 == g.D) {
-            nxt.z0 = 0;
-            ++nxt.n;
-          }
-        }
-      }
-      if constexpr (DMA) set_xd(nxt);
-      else set_x(nxt);
-    }
-    const T* Xb = Xl + b * XQ * EPQ;
-    // group q = (kz, kx) = divmod(q, 3): the 6 halo rows of plane wave + kz at shift kx
-    V8<T> af[2][HY];
-    auto load_group = [&](V8<T> (&f)[HY], int q) {
-      const int kz = q / 3, kx = q - kz * 3;
-#pragma unroll
-      for (int h = 0; h < HY; ++h) f[h].load(Xb + (ao[kx] + kz * RZ + h * RY) * EPQ);
-    };
-    stamp();
-    load_group(af[0], 0);
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-      if (q + 1 < 9) load_group(af[(q + 1) & 1], q + 1);
-      // the next brick's halo: 4 rows loaded in each of groups 0..2, 2 rows stored in each of groups 3..8,
-      // so the loads' issue and the LDS writes overlap MFMAs
-      if (unext) {
-        if constexpr (DMA) {
-          if (q < 3) issue_xd(b ^ 1, 4 * q, 4 * q + 4 < DK ? 4 * q + 4 : DK);
-        } else {
-          if (q < 3) load_x(4 * q, 4 * q + 4);
-          else store_x(b ^ 1, 2 * (q - 3), 2 * (q - 3) + 2);
-        }
-      }
-      if (q == 5) stamp();
-      if constexpr (INP) {
-        if (q == 4) in_load(cur);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // keep the next group's reads ahead of this group's MFMAs
-      // the previous brick's outputs: their VALU work and stores fill the first group's MFMA shadow
-      if (q == 0 && u > u_begin) epilogue(prev);
-      const int kz = q / 3, kx = q - kz * 3;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int i = 0; i < BY; ++i)
-#pragma unroll
-          for (int j = 0; j < RN; ++j) mfma_aw(acc[i][j], wf[kz * 9 + ky * 3 + kx][j].v, af[q & 1][i + ky].v);
-    }
-#pragma unroll
-    for (int i = 0; i < BY; ++i) brick4_fence(acc[i][0], acc[i][1]);
-    stamp();
-#pragma unroll
-    for (int i = 0; i < BY; ++i)
-#pragma unroll
-      for (int j = 0; j < RN; ++j) ev[i][j] = acc[i][j];
-    prev = cur;
-    stamp();
-    if constexpr (DMA) __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the next halo has landed
-    __syncthreads();   // buffer b^1 is complete; buffer b is free for the brick after next
-    b ^= 1;
-    cur = nxt;
-  }
-  epilogue(prev);
-  if constexpr (INP) in_flush();
-}
-
-// ------------------------------------------------- brick conv v6 (brick5 with its other work between the MFMAs)
-// Stamps and the .s of brick5 (r03s, 96^3 B=2 32->32 forward, one wave per SIMD): ~8,000 cycles per brick against
-// 3,456 of MFMA issue.  hipcc emitted each group's halo staging (the deferred norm's VALU work and its ds_writes),
-// the next group's fragment reads and the previous brick's epilogue as blocks BETWEEN the groups' MFMA runs, and
-// an MFMA run at one wave per SIMD leaves only 8 of every 16 cycles to other instructions -- when those come as a
-// block, the matrix pipe idles for the whole block.  v6 is brick5's register-staged path (same layout, same
-// arithmetic, bitwise the same outputs) with every group cut into 8 chunks of 3 MFMAs separated by
-// sched_barrier(0), each chunk carrying a fixed share of the rest: one of the next group's 6 fragment reads, a row
-// of the next brick's halo loads (groups 0-1), one 2-channel pair of a staged row's deferred norm (groups SG0..8,
-// row written to LDS with its fourth pair) or one row of the previous brick's epilogue (group 0).  The steady state
-// has no branches: NORM is a template parameter, out-of-volume rows are zeroed by a mask instead of a branch, the
-// 40 threads without a halo column write a dummy LDS slot, the last brick re-stages itself, and the first brick's
-// group-0 epilogue writes bias-only values that the next brick's epilogue (same lanes, same addresses) overwrites.
-// DBG (timing probes only, wrong results): 1 = MFMAs + fragment reads only after the prologue, 2 = MFMAs only.
-// INP (data gradient, no bias): the epilogue also sums the InstanceNorm-backward partials of its output, as brick5's
-// INP variant (same per-lane order: bitwise the same partials); the x of a brick's output voxels is loaded in its
-// group 4, its partial sums are formed in the next brick's group 1.
+// Requirements (host): bf16, one 32-channel K chunk, Ncols % 32 == 0, D % 4, H % 4, W % 16.
+// Its predecessor v5 (same layout, same arithmetic, bitwise the same outputs; removed) measured ~8,000 cycles per
+// brick against 3,456 of MFMA issue (r03s, 96^3 B=2 32->32 forward, one wave per SIMD).  hipcc emitted each group's
+// halo staging (the deferred norm's VALU work and its ds_writes), the next group's fragment reads and the previous
+// brick's epilogue as blocks BETWEEN the groups' MFMA runs, and an MFMA run at one wave per SIMD leaves only 8 of
+// every 16 cycles to other instructions -- when those come as a block, the matrix pipe idles for the whole block.  v6
+// cuts every group into 8 chunks of 3 MFMAs separated by sched_barrier(0), each chunk carrying a fixed share of the
+// rest: one of the next group's 6 fragment reads, a row of the next brick's halo loads (groups 0-1), one 2-channel
+// pair of a staged row's deferred norm (groups SG0..8, row written to LDS with its fourth pair) or one row of the
+// previous brick's epilogue (group 0).  The steady state has no branches: NORM is a template parameter, out-of-volume
+// rows are zeroed by a mask instead of a branch, the 40 threads without a halo column write a dummy LDS slot, the
+// last brick re-stages itself, and the first brick's group-0 epilogue writes bias-only values that the next brick's
+// epilogue (same lanes, same addresses) overwrites.
+// INP (data gradient, no bias): the epilogue also sums the InstanceNorm-backward partials of its output
+// (GemmArgs::inpart; fixed per-lane order); the x of a brick's output voxels is loaded in its group 4, its partial
+// sums are formed in the next brick's group 1.
 // F8 (forward only; mixed bf16/fp8 of config c5): the halo is staged as OCP e4m3 (the first 8 bytes of each 16-B
 // quad, read by ds_read_b64), the weights come as e4m3 w * s[co] (mmseg_pack_conv3_fp8) and the MFMA is
 // v_mfma_f32_16x16x32_fp8_fp8 with fp32 accumulation; the epilogue multiplies by g.wdq[co] = 1 / s[co].
-template <bool NORM, int SG0 = 3, int DBG = 0, bool INP = false, bool F8 = false>
+template <bool NORM, int SG0 = 3, bool INP = false, bool F8 = false>
 __global__ __launch_bounds__(256, 1) void conv3_brick6_kernel(GemmArgs g, int upb, int blocks_per_nt) {
   PROBE_BLOCK(false);
   using T = bf16_t;
@@ -2062,21 +1651,21 @@ __global__ __launch_bounds__(256, 1) void conv3_brick6_kernel(GemmArgs g, int up
       const int kz = q / 3, kx = q - kz * 3;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        if (q + 1 < 9 && c < HY && DBG < 2) {     // fragment c of the next group
+        if (q + 1 < 9 && c < HY) {     // fragment c of the next group
           const int qn = q + 1, kzn = qn / 3, kxn = qn - kzn * 3;
           if constexpr (F8) af8[qn & 1][c] = *reinterpret_cast<const long*>(Xb + (ao[kxn] + kzn * RZ + c * RY) * EPQ);
           else af[qn & 1][c].load(Xb + (ao[kxn] + kzn * RZ + c * RY) * EPQ);
         }
-        if (q == 0 && DBG == 0) {
+        if (q == 0) {
           load_row(c);                  // next brick's halo rows 0..7
           if ((c & 1) == 0) epi_row(prev, c >> 1);
         }
-        if (q == 1 && c < XK - 8 && DBG == 0) load_row(8 + c);
+        if (q == 1 && c < XK - 8) load_row(8 + c);
         if constexpr (INP) {
-          if (q == 1 && DBG == 0) epi_inp(c >> 1, c & 1);
-          if (q == 4 && c < BY && DBG == 0) in_load_row(cur, c);
+          if (q == 1) epi_inp(c >> 1, c & 1);
+          if (q == 4 && c < BY) in_load_row(cur, c);
         }
-        if (q >= SG0 && DBG == 0) {
+        if (q >= SG0) {
 #pragma unroll
           for (int pp = 0; pp < PPC; ++pp) {
             const int pi = c * PPC + pp;            // pair index inside the group: row slot pi / 4, pair pi % 4
@@ -2152,25 +1741,10 @@ __host__ __device__ constexpr int br_xq(int tsize) { return tsize == 2 ? 2560 : 
 // the same barriers; half 1's accumulators are added to half 0's through LDS (fixed order) before the epilogue.
 // At these levels a launch has ~256 blocks, one per CU, so the KW = 1 form runs ONE wave per SIMD and nothing
 // hides a wave's staging and LDS latency; two K-halves give every SIMD a second wave without a global split.
-template <typename T, int BN, int CBZ = 0, int CBY = 0, int CBX = 0, int DBG = 0, bool PF = false, bool B32 = false,
-          int KW = 1>
+template <typename T, int BN, int CBZ = 0, int CBY = 0, int CBX = 0, bool PF = false, bool B32 = false, int KW = 1>
 __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void conv3_brickr_kernel(
-    GemmArgs g, int bz_rt, int by_rt, int bx_rt, long long* dbg = nullptr) {
+    GemmArgs g, int bz_rt, int by_rt, int bx_rt) {
   const int bz = CBZ > 0 ? CBZ : bz_rt, by = CBY > 0 ? CBY : by_rt, bx = CBX > 0 ? CBX : bx_rt;
-  // DBG 4: every block's (realtime, memtime) at start / end, block 0 wave 0's per-phase memtime stamps
-  int dn = 0;
-  auto stamp = [&]() {
-    if constexpr (DBG == 4) {
-      if (blockIdx.x == 0 && threadIdx.x == 0 && dn < 64) dbg[4 * 4096 + dn++] = (long long)__builtin_amdgcn_s_memtime();
-    }
-  };
-  if constexpr (DBG == 4) {
-    if (threadIdx.x == 0) {
-      dbg[4 * blockIdx.x + 0] = (long long)__builtin_amdgcn_s_memrealtime();
-      dbg[4 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memtime();
-    }
-  }
-  stamp();
   using L = Brick2Layout<T>;
   constexpr int RM = 4, RN = BN / 16;
   constexpr int XQ = br_xq(sizeof(T));
@@ -2320,7 +1894,6 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
     store_w();
   }
   __syncthreads();
-  stamp();
   for (int it = 0; it < n_iter; ++it) {
     const int st = st_begin + it;
     const bool active = st < st_end;   // (KW = 2: half 1 may own one chunk fewer; it still joins every barrier)
@@ -2328,7 +1901,7 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
     const int sn = st + 1;
     const bool more = sn < st_end;
     const int cn = sn / 3, kzn = sn - cn * 3;
-    if (more && DBG != 1) {
+    if (more) {
       load_w(cn, kzn);
       if (kzn == 0) load_x(cn);
     }
@@ -2365,27 +1938,17 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
       for (int j = 0; j < RN; ++j) bf[j].load(Wl + (t9 * BN * L::QV + bq[j]) * EPQ);
 #pragma unroll
       for (int i = 0; i < RM; ++i) af[i].load(Xl + (aq[i] + hoff) * EPQ);
-      if (DBG == 2) {
 #pragma unroll
-        for (int i = 0; i < RM; ++i)
+      for (int i = 0; i < RM; ++i)
 #pragma unroll
-          for (int j = 0; j < RN; ++j) acc[i][j][0] += (float)af[i].get(0) * (float)bf[j].get(1);
-      } else {
-#pragma unroll
-        for (int i = 0; i < RM; ++i)
-#pragma unroll
-          for (int j = 0; j < RN; ++j) mfma_step<T>(acc[i][j], af[i], bf[j]);
-      }
+        for (int j = 0; j < RN; ++j) mfma_step<T>(acc[i][j], af[i], bf[j]);
     }
-    stamp();
     __syncthreads();
-    stamp();
-    if (more && DBG != 3) {
+    if (more) {
       store_w();
       if (kzn == 0) store_x();
     }
-    if (KW > 1 || (more && DBG != 3)) __syncthreads();   // (KW = 2: the halves' `more` may differ)
-    stamp();
+    if (KW > 1 || more) __syncthreads();   // (KW = 2: the halves' `more` may differ)
   }
 
   // KW = 2: half 1's accumulators added to half 0's (the loop ended with a barrier: the stage buffers are free)
@@ -2432,11 +1995,6 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
       }
     }
     __syncthreads();
-    if (KW == 1 && g.stats) {
-      float* red = reinterpret_cast<float*>(El + 256 * EP);
-      const long long brick = (long long)n * (bz_n * by_n * bx_n) + ((long long)bzi * by_n + byi) * bx_n + bxi;
-      brick_in_stats<T, BN>(El, EP, rows, red, g.stats, brick, n0, g.Ncols);
-    }
     T* O = reinterpret_cast<T*>(g.out);
     constexpr int CG = BN / 8;
     for (int e = etid; e < rows * CG; e += ET) {
@@ -2470,14 +2028,6 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
         const float4 v = *reinterpret_cast<const float4*>(El + rr * EP + cg * 4);
         *reinterpret_cast<float4*>(g.part + ((long long)ks * g.M + row_vox(rr)) * g.Ncols + col) = v;
       }
-    }
-  }
-  if constexpr (DBG == 4) {
-    stamp();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      dbg[4 * blockIdx.x + 2] = (long long)__builtin_amdgcn_s_memrealtime();
-      dbg[4 * blockIdx.x + 3] = (long long)__builtin_amdgcn_s_memtime();
     }
   }
 }
@@ -2556,11 +2106,11 @@ Conv3Plan plan_conv3(int M, int Ncols, int cin, int D, int H, int W, int lda, in
   return p;
 }
 
-// True when launch_gemm<bf16, CONV3> runs conv3_brick5_kernel for this shape (the only conv kernel that
+// True when launch_gemm<bf16, CONV3> runs conv3_brick6_kernel for this shape (the only conv kernel that
 // applies a deferred InstanceNorm + ReLU to its A source): the conditions of its branch in launch_gemm and of
 // every branch taken before it.
-bool brick5_selected(const GemmArgs& g, int tsize) {
-  if (tsize != 2 || g.ksplit != 1 || g.stats != nullptr) return false;
+bool brick6_selected(const GemmArgs& g, int tsize) {
+  if (tsize != 2 || g.ksplit != 1) return false;
   const Conv3Plan plan = plan_conv3(g.M, g.Ncols, 8 << g.cpg_shift, g.D, g.H, g.W, g.lda, g.ldo, tsize);
   if (plan.kind != 1) return false;
   const int nb1 = (g.M / (g.D * g.H * g.W)) * (g.D / 4) * (g.H / B2_Y) * (g.W / B2_X);
@@ -2583,38 +2133,31 @@ inline bool tile_in_pitch(const GemmArgs& g, int BN) { return (long long)((g.Nco
   } while (0)
 
 // The W % 16 one-chunk 32-column conv: brick6 (forward, deferred-norm forward, e4m3 forward, and the data gradient
-// with the InstanceNorm-backward partials); brick5 only for a partials launch with a bias term (never on the
-// engine's path: a data gradient has no bias).  Returns the bricks per block.
-int launch_brick5(const GemmArgs& g, hipStream_t s) {
+// with the InstanceNorm-backward partials).  Returns the bricks per block.
+int launch_brick6(const GemmArgs& g, hipStream_t s) {
   const int nt_n = g.Ncols / 32;
   const int per_nt = std::max(1, knob("MMSEG_BRICK4_BLOCKS", 256) / nt_n);
-  const int nb5 = (g.M / (g.D * g.H * g.W)) * (g.D / 4) * (g.H / 4) * (g.W / 16);
-  const int upb5 = ceil_div(nb5, std::min(per_nt, nb5));
-  const int bpn5 = ceil_div(nb5, upb5);
-  const dim3 grid(bpn5 * nt_n), block(256);
+  const int nb6 = (g.M / (g.D * g.H * g.W)) * (g.D / 4) * (g.H / 4) * (g.W / 16);
+  const int upb6 = ceil_div(nb6, std::min(per_nt, nb6));
+  const int bpn6 = ceil_div(nb6, upb6);
+  const dim3 grid(bpn6 * nt_n), block(256);
   if (g.wdq) {   // e4m3 forward (mmseg_conv3_fwd_fp8)
     MMSEG_TILE(g, "conv3_brick6_kernel<BN32,F8>", 32);
-    if (g.nmean) MMSEG_LAUNCH((conv3_brick6_kernel<true, 6, 0, false, true>), grid, block, 0, s, g, upb5, bpn5);
-    else MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, 0, false, true>), grid, block, 0, s, g, upb5, bpn5);
-    return upb5;
+    if (g.nmean) MMSEG_LAUNCH((conv3_brick6_kernel<true, 6, false, true>), grid, block, 0, s, g, upb6, bpn6);
+    else MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, false, true>), grid, block, 0, s, g, upb6, bpn6);
+    return upb6;
   }
-  if (g.inpart) {   // samples a block does not touch keep zero partials
-    if (!g.bias) {   // (brick6 writes those zeros itself)
-      MMSEG_TILE(g, "conv3_brick6_kernel<BN32,INP>", 32);
-      MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, 0, true>), grid, block, 0, s, g, upb5, bpn5);
-      return upb5;
-    }
-    MMSEG_TILE(g, "conv3_brick5_kernel<BN32>", 32);
-    hipMemsetAsync(g.inpart, 0, sizeof(float) * 2 * (size_t)(g.M / (g.D * g.H * g.W)) * bpn5 * g.Ncols, s);
-    MMSEG_LAUNCH((conv3_brick5_kernel<false, true, true>), grid, block, 0, s, g, upb5, bpn5, nullptr);
-    return upb5;
+  if (g.inpart) {   // mmseg_conv3_dgrad_in (no bias); the kernel zeroes the partials of samples a block does not touch
+    MMSEG_TILE(g, "conv3_brick6_kernel<BN32,INP>", 32);
+    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, true>), grid, block, 0, s, g, upb6, bpn6);
+    return upb6;
   }
   MMSEG_TILE(g, "conv3_brick6_kernel<BN32>", 32);
   if (g.nmean)
-    MMSEG_LAUNCH((conv3_brick6_kernel<true, 6>), grid, block, 0, s, g, upb5, bpn5);
+    MMSEG_LAUNCH((conv3_brick6_kernel<true, 6>), grid, block, 0, s, g, upb6, bpn6);
   else
-    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6>), grid, block, 0, s, g, upb5, bpn5);
-  return upb5;
+    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6>), grid, block, 0, s, g, upb6, bpn6);
+  return upb6;
 }
 
 // 4 consecutive columns per thread in gemm_splitk_reduce (for the transposed conv: 4 channels of one child voxel,
@@ -2776,7 +2319,6 @@ struct WgradArgs {
   // activation, staged as relu((x - nmean[n][c]) * nrstd[n][c]) rounded to T
   const float* nmean;
   const float* nrstd;
-  int dbg;   // brick weight-gradient timing probe (diagnostics builds): 1 = no global loads after the first brick, 2 = no MFMA
   int frag;  // wgrad_dma: split partials in the fragment-native layout (wgrad_dma_mt, WReduceArgs::frag_mt)
   int groups;  // grouped launch (wgrad_brickr only): the bricks are `groups` equal sample groups, splits
                // [gi * ksplit / groups, (gi + 1) * ksplit / groups) cover group gi's bricks only
@@ -3578,13 +3120,11 @@ __global__ __launch_bounds__(512, (MT == 2 && V == 2) ? 2 : 1) void wgrad_brick2
     __syncthreads();
     for (long long b = b_begin; b < b_end; ++b) {
       const bool more = b + 1 < b_end;
-      if (more && g.dbg != 1) load_into(b + 1, dr, xr, xin, xn);
-      if (g.dbg != 2) {
-        if constexpr (PIPE)
-          compute_pipe(buf, tcc);
-        else
-          compute(buf);
-      }
+      if (more) load_into(b + 1, dr, xr, xin, xn);
+      if constexpr (PIPE)
+        compute_pipe(buf, tcc);
+      else
+        compute(buf);
       if (more) store_from(buf ^ 1, dr, xr, xin, xn);
       __syncthreads();
       buf ^= 1;
@@ -3633,7 +3173,7 @@ __global__ __launch_bounds__(512, (MT == 2 && V == 2) ? 2 : 1) void wgrad_brick2
 // LDS slot (pads and out-of-volume voxels read zeros through the OOB offset).  Each staged weight slice feeds
 // 8 waves x 9 taps x 4 ZP x RN MFMAs (twice conv3_brick2's).  LDS 141 KB (BN 64) / 155 KB (BN 32): one block per
 // CU, two waves per SIMD.  Requirements (host): bf16, Cin % 32 == 0, Ncols % BN == 0, D % 8 ZP, H % 8, W % 8, ksplit == 1, no
-// fused stats / deferred norm / IN partials, the A and B extents < 2^31 bytes.
+// deferred norm / IN partials, the A and B extents < 2^31 bytes.
 template <int BN, int ZP>
 __global__ __launch_bounds__(512, 1) void conv3_brick8_kernel(GemmArgs g) {
   PROBE_BLOCK(false);
@@ -4089,14 +3629,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradArgs g) {
   for (int b = b_begin, sc = 0; b < b_end; ++b, sc = sc + 1 == NST ? 0 : sc + 1) {
     // issue brick b + NST - 1 into the stage brick b - 1 used (every wave passed the barrier after it)
     const int sn = sc == 0 ? NST - 1 : sc - 1;
-    if (b + NST - 1 < b_end && g.dbg != 1) issue(st + sn * SS, b + NST - 1);
+    if (b + NST - 1 < b_end) issue(st + sn * SS, b + NST - 1);
     const int sb = 0;
-    if (g.dbg != 2) {
-      if constexpr (PIPE)
-        compute_pipe(st + sc * SS, sb, tcc);
-      else
-        compute(st + sc * SS, sb);
-    }
+    if constexpr (PIPE)
+      compute_pipe(st + sc * SS, sb, tcc);
+    else
+      compute(st + sc * SS, sb);
     // brick b + 1 has landed once at most min(NST - 2, bricks issued after it) bricks are in flight
     {
       const int after = b_end - b - 2 < NST - 2 ? b_end - b - 2 : NST - 2;
@@ -5290,11 +4828,11 @@ int launch_splitk_reduce(const GemmArgs& g, hipStream_t s) {
 
 template <typename T, int MODE>
 int launch_gemm(GemmArgs g, hipStream_t s) {
-  if (g.nmean) {   // deferred InstanceNorm + ReLU of A: brick5 only (mmseg_conv3_norm_ok)
-    MMSEG_REQUIRE(MODE == MODE_CONV3 && brick5_selected(g, (int)sizeof(T)),
-                  "conv3 with a deferred norm needs the brick5 kernel for this shape (mmseg_conv3_norm_ok)");
-    launch_brick5(g, s);
-    return mmseg::check_launch("conv3_brick5_norm");
+  if (g.nmean) {   // deferred InstanceNorm + ReLU of A: brick6 only (mmseg_conv3_norm_ok)
+    MMSEG_REQUIRE(MODE == MODE_CONV3 && brick6_selected(g, (int)sizeof(T)),
+                  "conv3 with a deferred norm needs the brick6 kernel for this shape (mmseg_conv3_norm_ok)");
+    launch_brick6(g, s);
+    return mmseg::check_launch("conv3_brick6_norm");
   }
   const int Cbig = g.Ncols >= 64;
   dim3 block(256);
@@ -5320,51 +4858,51 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
       if constexpr (sizeof(T) == 2) {
         MMSEG_TILE(g, "conv3_brickr_kernel<BN64>", 64);
         if (b666 && rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6, 0, false, true>), grid, block, 0, s, g, 6, 6, 6, (long long*)nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6, false, true>), grid, block, 0, s, g, 6, 6, 6);
         else if (b666)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6, (long long*)nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6);
         else if (b488 && rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8, 0, false, true>), grid, block, 0, s, g, 4, 8, 8, (long long*)nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8, false, true>), grid, block, 0, s, g, 4, 8, 8);
         else if (b488)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8, (long long*)nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8);
         else if (rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 0, 0, 0, 0, false, true>), grid, block, 0, s, g, plan.bz,
-                             plan.by, plan.bx, (long long*)nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 0, 0, 0, false, true>), grid, block, 0, s, g, plan.bz, plan.by,
+                       plan.bx);
         else
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64>), grid, block, 0, s, g, plan.bz, plan.by, plan.bx, (long long*)nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64>), grid, block, 0, s, g, plan.bz, plan.by, plan.bx);
       }
     } else if (b666) {
       // KW = 2: two waves per SIMD from an in-block split of the chunks (see the kernel); tap t + 1's fragments
       // read during tap t's MFMAs (PF: at 12^3 / 6^3 a CU holds one block; 5-10 % per launch, r04ab convbench)
-      const bool kw2 = sizeof(T) == 2 && !g.stats && cps >= 2;
+      const bool kw2 = sizeof(T) == 2 && cps >= 2;
       MMSEG_TILE(g, kw2 ? "conv3_brickr_kernel<BN32,KW2>" : "conv3_brickr_kernel<BN32>", 32);
       bool done = false;
       if constexpr (sizeof(T) == 2) {   // (the fp32 form's two stage sets exceed the LDS)
         const dim3 b2(512);
         if (kw2 && rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, 0, true, true, 2>), grid, b2, 0, s, g, 6, 6, 6, nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, true, 2>), grid, b2, 0, s, g, 6, 6, 6);
         else if (kw2)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, 0, true, false, 2>), grid, b2, 0, s, g, 6, 6, 6, nullptr);
+          MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, false, 2>), grid, b2, 0, s, g, 6, 6, 6);
         done = kw2;
       }
       if (done) {
       } else if (rb32)
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, 0, true, true>), grid, block, 0, s, g, 6, 6, 6, (long long*)nullptr);
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, true>), grid, block, 0, s, g, 6, 6, 6);
       else
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6, (long long*)nullptr);
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6);
     } else if (b488) {
       MMSEG_TILE(g, "conv3_brickr_kernel<BN32>", 32);
       if (rb32)
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8, 0, false, true>), grid, block, 0, s, g, 4, 8, 8, (long long*)nullptr);
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8, false, true>), grid, block, 0, s, g, 4, 8, 8);
       else
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8, (long long*)nullptr);
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8);
     } else {
       MMSEG_TILE(g, "conv3_brickr_kernel<BN32>", 32);
       if (rb32)
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 0, 0, 0, 0, false, true>), grid, block, 0, s, g, plan.bz,
-                           plan.by, plan.bx, (long long*)nullptr);
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 0, 0, 0, false, true>), grid, block, 0, s, g, plan.bz, plan.by,
+                     plan.bx);
       else
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32>), grid, block, 0, s, g, plan.bz, plan.by, plan.bx, (long long*)nullptr);
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32>), grid, block, 0, s, g, plan.bz, plan.by, plan.bx);
     }
     if (mmseg::check_launch("conv3_brickr")) return 1;
     if (g.ksplit > 1) return launch_splitk_reduce<T, MODE>(g, s);
@@ -5382,7 +4920,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
       const int b8 = knob("MMSEG_BRICK8", 1);
       if (b8 && g.Ncols % 64 == 0 && (b8 == 2 || (g.Ncols == 64 && gemm_nchunk(g) >= 2)) && g.D % 8 == 0 &&
           g.H % 8 == 0 && g.W % 8 == 0 &&
-          g.stats == nullptr && g.nmean == nullptr && g.inpart == nullptr && g.ldo % 8 == 0 &&
+          g.nmean == nullptr && g.inpart == nullptr && g.ldo % 8 == 0 &&
           (!g.out2 || g.ldo2 % 8 == 0) && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0 &&
           nb8 * (g.Ncols / 64) >= knob("MMSEG_BRICK8_MINBLK", 256) &&
           (long long)g.M * g.lda * 2 < (1LL << 31) && (long long)((g.KG + 3) & ~3) * g.Cpad * 16 < (1LL << 31)) {
@@ -5391,7 +4929,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
         return mmseg::check_launch("conv3_brick8");
       }
       if (b8 && g.Ncols == 32 && g.D % 16 == 0 && g.H % 8 == 0 && g.W % 8 == 0 &&
-          g.stats == nullptr && g.nmean == nullptr && g.inpart == nullptr && g.ldo % 8 == 0 &&
+          g.nmean == nullptr && g.inpart == nullptr && g.ldo % 8 == 0 &&
           (!g.out2 || g.ldo2 % 8 == 0) && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0 &&
           nb8 / 2 >= knob("MMSEG_BRICK8_MINBLK", 256) && (8 << g.cpg_shift) >= 64 &&
           (long long)g.M * g.lda * 2 < (1LL << 31) && (long long)((g.KG + 3) & ~3) * g.Cpad * 16 < (1LL << 31)) {
@@ -5403,7 +4941,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
     // v3 is bf16 only: its fp32 instantiation (f32 16x16x4 MFMA with swapped operands) returned the first
     // row of each 4-row accumulator group in all four registers (tools/diag_b3.py); the fp32 parity path
     // keeps the v2 kernel.
-    const bool v3 = sizeof(T) == 2 && g.stats == nullptr && (long long)g.M * g.lda * (long long)sizeof(T) < (1LL << 31);
+    const bool v3 = sizeof(T) == 2 && (long long)g.M * g.lda * (long long)sizeof(T) < (1LL << 31);
     // persistent: at most one wave of resident blocks (2 per CU), each over a contiguous range of units
     const int maxblk = knob("MMSEG_BRICK3_BLOCKS", 512);
     // 32-bit offset halo staging (brick2 B32; bf16 only, see the runtime-brick branch)
@@ -5412,7 +4950,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
     // 48-column tiles also for multiples of 96 that are not of 64 (SwinUNETR's 96-column convs: two 48-column tiles
     // read the A halo twice, three 32-column brick3 tiles three times -- 128^3 96-column dgrad 0.74 ms at 706 TF/s
     // on brick3, r05c timer)
-    const bool bn48 = g.Ncols % 32 != 0 || (g.Ncols % 96 == 0 && g.Ncols % 64 != 0 && g.stats == nullptr);
+    const bool bn48 = g.Ncols % 32 != 0 || (g.Ncols % 96 == 0 && g.Ncols % 64 != 0);
     if (bn48) {    // a multiple of 48 (plan_conv3)
       MMSEG_TILE(g, "conv3_brick2_kernel<BN48,ZW1>", 48);
       if (b32) {
@@ -5428,7 +4966,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
         const int upb = ceil_div(nb1, std::min(per_nt, nb1));
         const int bpn = ceil_div(nb1, upb);
         if (g.H % 4 == 0 && g.W % 16 == 0 && g.ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0) {
-          launch_brick5(g, s);   // (16-B output stores)
+          launch_brick6(g, s);   // (16-B output stores)
         } else {
           MMSEG_TILE(g, "conv3_brick4_kernel<BN32>", 32);
           MMSEG_LAUNCH(conv3_brick4_kernel, dim3(bpn * nt_n), block, 0, s, g, upb, bpn);
@@ -5537,17 +5075,22 @@ int launch_gemm_mode(GemmArgs g, int mode, hipStream_t s) {
   return 1;
 }
 
+// 64-co row tiles for the brick weight-gradient kernels (brick2 / LDS-DMA and runtime brick), else 32-co.
+// A block's split partial is its whole tile, so at small volumes -- where the ~256 resident blocks each see a
+// few bricks -- the partials outweigh the inputs (24^3: 54 MB written and re-read per launch against 35-65 MB
+// of input); 32-co tiles halve them at the price of reading the halo once per row tile.  Below V voxels
+// a threshold the 32-co tiles were tried below (r04: equal or slower at 24^3), so 64-co tiles throughout.
+bool wgrad_co64(int Ca) { return Ca % 64 == 0; }
+
 // The LDS-DMA weight-gradient kernel's row tile (4 = 64 co, 2 = 32 co) when it takes this CONV3 brick2 launch,
 // else 0: bf16, byte offsets of both tensors within 31 bits (the deferred-norm variant keeps register staging by
 // default: its in-place LDS pass and extra barrier cost more than the DMA saves, 0.651 -> 0.682 ms/step for the
 // 32-co family)
-bool wgrad_co64(int Ca, long long V, int kind);
-
 int wgrad_dma_mt(const WgradArgs& g, int elem_bytes) {
   const bool dma = elem_bytes == 2 && g.brick == 2 && knob("MMSEG_WGRAD_DMA", 1) && g.nmean == nullptr &&
                    g.V * g.lda * 2 < (1LL << 31) &&
                    g.V * g.ldb * 2 < (1LL << 31) && (g.lda % 8) == 0 && (g.ldb % 8) == 0;
-  return dma ? (wgrad_co64(g.Ca, g.V, 2) ? 4 : 2) : 0;
+  return dma ? (wgrad_co64(g.Ca) ? 4 : 2) : 0;
 }
 
 // the row-slab weight gradient (wgrad_row_kernel) takes the shape: bf16 3^3, 32 output channels, W % 32 == 0,
@@ -5563,14 +5106,13 @@ bool wgrad_row_ok(const WgradArgs& g, int elem_bytes) {
 
 template <typename T, int MODE>
 int launch_wgrad(WgradArgs g, hipStream_t s) {
-  g.dbg = 0;   // (the timing probes of the brick weight-gradient kernels: 1 no loads, 2 no MFMA; diagnostics only)
   dim3 block(256);
   if constexpr (sizeof(T) == 2) {
     if (MODE == MODE_CONV3 && g.brick == 3) {
       const WBrick wb = plan_wgrad_brickr(g.D, g.H, g.W);
       const bool b366 = wb.bz == 3 && wb.by == 6 && wb.bx == 6;
       const bool b448 = wb.bz == 4 && wb.by == 4 && wb.bx == 8;   // grouped 48^3 / 24^3
-      if (wgrad_co64(g.Ca, g.V, 3)) {
+      if (wgrad_co64(g.Ca)) {
         dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 64) * g.ksplit);
         // (the compile-time bricks under their rocprofv3 family names, tools/rocprof_families.py)
         mmseg::note_kernel(b366 ? "wgrad_brickr_kernel<CO64,V3>" : b448 ? "wgrad_brickr_kernel<CO64,B448>"
@@ -5629,7 +5171,7 @@ int launch_wgrad(WgradArgs g, hipStream_t s) {
         }
         return mmseg::check_launch("wgrad_dma");
       }
-      if (wgrad_co64(g.Ca, g.V, 2)) {
+      if (wgrad_co64(g.Ca)) {
         dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 64) * g.ksplit);
         mmseg::note_kernel("wgrad_brick2_kernel<CO64,V3>");
         if (g.nmean)
@@ -5686,17 +5228,10 @@ int wgrad_brick_ok(int Ca, int cpg_shift, int D, int H, int W, int lda, int ldb,
 
 // Split count of the CONV3 brick wgrad: enough blocks to fill the chip, capped by
 // the caller's workspace (cap) and by one brick per split.
-// 64-co row tiles for the brick weight-gradient kernels (kind 2: brick2 / LDS-DMA, 3: runtime brick), else 32-co.
-// A block's split partial is its whole tile, so at small volumes -- where the ~256 resident blocks each see a
-// few bricks -- the partials outweigh the inputs (24^3: 54 MB written and re-read per launch against 35-65 MB
-// of input); 32-co tiles halve them at the price of reading the halo once per row tile.  Below V voxels
-// a threshold the 32-co tiles were tried below (r04: equal or slower at 24^3), so 64-co tiles throughout.
-bool wgrad_co64(int Ca, long long V, int kind) { return Ca % 64 == 0; }
-
 int brick_wgrad_splits(long long V, int cap, int Ca, int cpg_shift, int kind, int D, int H, int W,
                        int kchunks = 0) {
   const int nchunk = wgrad_nchunk(cpg_shift, kchunks);
-  const int tiles = nchunk * (Ca / ((kind >= 2 && wgrad_co64(Ca, V, kind)) ? 64 : 32));
+  const int tiles = nchunk * (Ca / ((kind >= 2 && wgrad_co64(Ca)) ? 64 : 32));
   // v2 / runtime-brick kernels: one wave of resident blocks (256 CUs x blocks per CU: 2 for the 32-co brick2
   // kernel, 1 for the 64-co and runtime-brick kernels, whose stage buffers take > 80 KB of LDS), never more:
   // a partial second wave of 512-thread blocks costs a whole block time.
@@ -5952,65 +5487,22 @@ int mmseg_pack_weights_batched(const void* descs, int n, long long total, int dt
 }
 
 // Generic implicit-GEMM: conv3 fwd / dgrad, 1x1, convT fwd / dgrad.
-// Bricks per sample whose InstanceNorm partials the CONV3 kernel for this shape
-// can emit from its epilogue (mmseg_conv_gemm_stats), or 0 when it cannot
-// (gather GEMM, split-K).  Every brick holds V / (bricks per sample) voxels.
-// The brick epilogues' fused statistics measured no net gain against the statistics pass (bench r01 q11; the
-// grouped form equal per step, r04ad), so no shape offers them: 0 for every shape (the ABI entry stays).
-int mmseg_conv3_stats_bricks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
-                             int dtype) {
-  return 0;
-}
-
-int mmseg_conv_gemm_stats(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                          float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
-                          int W, int ksplit, float* stats_part, int dtype, void* stream);
+// cin_real: the A source's channels past cin_real are padding (zero weights), so the CONV3 brick kernels skip the
+// 32-channel chunks wholly past it.  cin_real = 0: every channel is real.
+int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo, void* out2,
+                   int ldo2, int split, float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift,
+                   int D, int H, int W, int ksplit, int cin_real, int dtype, void* stream, int groups = 1,
+                   long long w_gstride = 0, int b_gstride = 0, const void* res = nullptr, int ldres = 0,
+                   int zcols = 0);
 
 int mmseg_conv_gemm(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
                     float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W,
                     int ksplit, int dtype, void* stream) {
-  return mmseg_conv_gemm_stats(a, lda, wpacked, bias, out, ldo, splitk_ws, mode, M, Ncols, Cpad, KG, cpg_shift, D, H,
-                               W, ksplit, nullptr, dtype, stream);
+  return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, nullptr, 0, 0, splitk_ws, mode, M, Ncols, Cpad, KG,
+                        cpg_shift, D, H, W, ksplit, 0, dtype, stream);
 }
 
-int mmseg_conv_gemm_ex(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                       float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
-                       int W, int ksplit, float* stats_part, int cin_real, int dtype, void* stream);
-
-// mmseg_conv_gemm + per-brick InstanceNorm partials of the output (stats_part:
-// [N][bricks per sample][Ncols][2] floats, see mmseg_conv3_stats_bricks).
-int mmseg_conv_gemm_stats(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                          float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
-                          int W, int ksplit, float* stats_part, int dtype, void* stream) {
-  return mmseg_conv_gemm_ex(a, lda, wpacked, bias, out, ldo, splitk_ws, mode, M, Ncols, Cpad, KG, cpg_shift, D, H, W,
-                            ksplit, stats_part, 0, dtype, stream);
-}
-
-// mmseg_conv_gemm_stats for an A source whose channels past cin_real are padding (zero weights): the CONV3
-// brick kernels skip the 32-channel chunks wholly past cin_real.  cin_real = 0: every channel is real.
-int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo, void* out2,
-                   int ldo2, int split, float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift,
-                   int D, int H, int W, int ksplit, float* stats_part, int cin_real, int dtype, void* stream,
-                   int groups = 1, long long w_gstride = 0, int b_gstride = 0, const void* res = nullptr,
-                   int ldres = 0, int zcols = 0);
-int mmseg_conv3_group_stats_bricks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
-                                   int ldo, int dtype);
-
-// mmseg_conv_gemm_group + the per-brick InstanceNorm partials of the output (stats_part [M / (D H W)]
-// [mmseg_conv3_group_stats_bricks()][Ncols][2], (mean, M2) per brick; mmseg_instnorm_stats_bricks merges them)
-// from the runtime-brick kernel's epilogue -- the grouped 48^3 / 24^3 levels' statistics without a pass over
-// the conv output.
-int mmseg_conv_gemm_group_stats(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                                int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W,
-                                int cin_real, int groups, long long w_gstride, int b_gstride, float* stats_part,
-                                int dtype, void* stream) {
-  MMSEG_REQUIRE(mode == MODE_CONV3 && groups >= 1 && M % (groups * D * H * W) == 0 && stats_part != nullptr,
-                "conv_gemm_group_stats: CONV3 over groups x whole samples, with a statistics buffer");
-  return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, nullptr, 0, 0, nullptr, mode, M, Ncols, Cpad, KG, cpg_shift,
-                        D, H, W, 1, stats_part, cin_real, dtype, stream, groups, w_gstride, b_gstride);
-}
-
-// mmseg_conv_gemm_ex over `groups` equal sample groups of A / out with their own packed weights (group gi:
+// mmseg_conv_gemm over `groups` equal sample groups of A / out with their own packed weights (group gi:
 // wpacked + gi * w_gstride elements) and bias (bias + gi * b_gstride): the modality encoders' small levels as one
 // launch (+ one split-K reduce).  Runtime-brick CONV3 shapes only (small volumes).
 int mmseg_conv_gemm_group(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
@@ -6020,23 +5512,16 @@ int mmseg_conv_gemm_group(const void* a, int lda, const void* wpacked, const flo
   MMSEG_REQUIRE(mode == MODE_CONV3 && groups >= 1 && M % (groups * D * H * W) == 0,
                 "conv_gemm_group: CONV3 over groups x whole samples");
   return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, nullptr, 0, 0, splitk_ws, mode, M, Ncols, Cpad, KG, cpg_shift,
-                        D, H, W, ksplit, nullptr, cin_real, dtype, stream, groups, w_gstride, b_gstride);
+                        D, H, W, ksplit, cin_real, dtype, stream, groups, w_gstride, b_gstride);
 }
 
-int mmseg_conv_gemm_ex(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
-                       float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
-                       int W, int ksplit, float* stats_part, int cin_real, int dtype, void* stream) {
-  return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, nullptr, 0, 0, splitk_ws, mode, M, Ncols, Cpad, KG,
-                        cpg_shift, D, H, W, ksplit, stats_part, cin_real, dtype, stream);
-}
-
-// mmseg_conv_gemm_ex (no statistics) with the whole-row output hint: columns [Ncols, zcols) of the output rows are
-// written as zeros by the kernels that support it (the brick2 conv kernels), left alone by the others.
+// mmseg_conv_gemm (channel-padded A source: cin_real) with the whole-row output hint: columns [Ncols, zcols) of the
+// output rows are written as zeros by the kernels that support it (the brick2 conv kernels), left alone by the others.
 int mmseg_conv_gemm_zw(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
                        float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
                        int W, int ksplit, int cin_real, int zcols, int dtype, void* stream) {
   return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, nullptr, 0, 0, splitk_ws, mode, M, Ncols, Cpad, KG,
-                        cpg_shift, D, H, W, ksplit, nullptr, cin_real, dtype, stream, 1, 0, 0, nullptr, 0, zcols);
+                        cpg_shift, D, H, W, ksplit, cin_real, dtype, stream, 1, 0, 0, nullptr, 0, zcols);
 }
 
 // 1x1 GEMM (MODE_POINT, ksplit 1) with the MLP's GELU in its epilogue: epi 1, out = h = A W^T + bias and gelu_out
@@ -6053,7 +5538,7 @@ int mmseg_conv_gemm_gelu(const void* a, int lda, const void* wpacked, const floa
                 "conv_gemm_gelu: ldo, Ncols multiples of 8, 16-B aligned buffers");
   const int KGp = (KG + 3) & ~3;
   GemmArgs g{a, lda, wpacked, bias, out, ldo, nullptr, M, Ncols, Cpad, KG, 0, 1, 1, 1, 1, KGp,
-             1 /* XCD-aware block remap */, nullptr, 0, nullptr, nullptr};
+             1 /* XCD-aware block remap */, 0, nullptr, nullptr};
   MMSEG_REQUIRE(lda % 8 == 0, "conv_gemm_gelu: lda must be a multiple of 8");
   MMSEG_REQUIRE(Cpad >= ((Ncols + (Ncols >= 64 ? 63 : 31)) / (Ncols >= 64 ? 64 : 32)) * (Ncols >= 64 ? 64 : 32),
                 "conv_gemm_gelu: packed weights must be padded to the column tile (Cpad=%d, Ncols=%d)", Cpad, Ncols);
@@ -6072,11 +5557,11 @@ int mmseg_conv_gemm_res(const void* a, int lda, const void* wpacked, const float
                         void* out, int ldo, int M, int Ncols, int Cpad, int KG, int dtype, void* stream) {
   MMSEG_REQUIRE(res != nullptr, "conv_gemm_res: residual required");
   return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, nullptr, 0, 0, nullptr, MODE_POINT, M, Ncols, Cpad, KG, 0, 1,
-                        1, 1, 1, nullptr, 0, dtype, stream, 1, 0, 0, res, ldres);
+                        1, 1, 1, 0, dtype, stream, 1, 0, 0, res, ldres);
 }
 
-// mmseg_conv_gemm_ex (no fused statistics) whose output columns [split, Ncols) go to a second tensor out2 (row
-// pitch ldo2) as columns 0..: the decoder's first-conv data gradient writes d(upsampled) and d(skip) dense.
+// mmseg_conv_gemm (channel-padded A source: cin_real) whose output columns [split, Ncols) go to a second tensor out2
+// (row pitch ldo2) as columns 0..: the decoder's first-conv data gradient writes d(upsampled) and d(skip) dense.
 int mmseg_conv_gemm_split(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo,
                           void* out2, int ldo2, int split, float* splitk_ws, int mode, int M, int Ncols, int Cpad,
                           int KG, int cpg_shift, int D, int H, int W, int ksplit, int cin_real, int dtype,
@@ -6086,13 +5571,13 @@ int mmseg_conv_gemm_split(const void* a, int lda, const void* wpacked, const flo
                 "conv_gemm_split: split %d must be a multiple of 8 inside (0, %d), ldo / ldo2 multiples of 8, out2 "
                 "16-B aligned", split, Ncols);
   return conv_gemm_impl(a, lda, wpacked, bias, out, ldo, out2, ldo2, split, splitk_ws, mode, M, Ncols, Cpad, KG,
-                        cpg_shift, D, H, W, ksplit, nullptr, cin_real, dtype, stream);
+                        cpg_shift, D, H, W, ksplit, cin_real, dtype, stream);
 }
 
 int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bias, void* out, int ldo, void* out2,
                    int ldo2, int split, float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift,
-                   int D, int H, int W, int ksplit, float* stats_part, int cin_real, int dtype, void* stream,
-                   int groups, long long w_gstride, int b_gstride, const void* res, int ldres, int zcols) {
+                   int D, int H, int W, int ksplit, int cin_real, int dtype, void* stream, int groups,
+                   long long w_gstride, int b_gstride, const void* res, int ldres, int zcols) {
   MMSEG_REQUIRE(zcols == 0 || (zcols >= Ncols && zcols % 8 == 0 && zcols <= ldo && !out2 && Ncols % 8 == 0 &&
                                zcols - Ncols <= 48),
                 "conv_gemm: whole-row extent zcols=%d must lie in [Ncols, min(ldo, Ncols + 48)]", zcols);
@@ -6102,12 +5587,6 @@ int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bia
                 "conv_gemm_res: MODE_POINT, ksplit 1, pitches and Ncols multiples of 8, 16-B aligned out / res");
   MMSEG_REQUIRE(cin_real >= 0 && cin_real <= (8 << cpg_shift), "conv_gemm: cin_real %d outside [0, %d]", cin_real,
                 8 << cpg_shift);
-  MMSEG_REQUIRE(!stats_part || (mode == MODE_CONV3 && ksplit == 1 &&
-                                (groups > 1 ? mmseg_conv3_group_stats_bricks(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda,
-                                                                             ldo, dtype)
-                                            : mmseg_conv3_stats_bricks(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo,
-                                                                       dtype)) > 0),
-                "conv_gemm_stats: fused statistics need a brick kernel without split-K for this shape");
   MMSEG_REQUIRE(lda % 8 == 0 && ldo >= 1, "conv_gemm: lda must be a multiple of 8 (got %d)", lda);
   MMSEG_REQUIRE(Cpad >= ((Ncols + (Ncols >= 64 ? 63 : 31)) / (Ncols >= 64 ? 64 : 32)) * (Ncols >= 64 ? 64 : 32),
                 "conv_gemm: packed weights must be padded to the column tile (Cpad=%d, Ncols=%d)", Cpad, Ncols);
@@ -6117,9 +5596,8 @@ int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bia
   int kps = ((ceil_div(KGp, ksplit) + 3) / 4) * 4;
   ksplit = ceil_div(KGp, kps);
   GemmArgs g{a, lda, wpacked, bias, out, ldo, splitk_ws, M, Ncols, Cpad, KG, cpg_shift, D, H, W, ksplit, kps,
-             1 /* XCD-aware block remap */, stats_part,
-             mode == MODE_CONV3 ? (cin_real + 31) / 32 : 0, nullptr, nullptr, out2,
-             ldo2, split};
+             1 /* XCD-aware block remap */, mode == MODE_CONV3 ? (cin_real + 31) / 32 : 0, nullptr, nullptr, out2, ldo2,
+             split};
   if (groups > 1) {
     g.grp_n = M / (D * H * W) / groups;
     g.w_gstride = w_gstride;
@@ -6133,7 +5611,7 @@ int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bia
   return launch_gemm_mode<float>(g, mode, s);
 }
 
-// 1 when mmseg_conv3_fwd_norm can run this shape (the brick5 kernel, the only conv forward that applies a
+// 1 when mmseg_conv3_fwd_norm can run this shape (the brick6 kernel, the only conv forward that applies a
 // deferred InstanceNorm + ReLU to its input): bf16, one 32-channel input chunk, 32 output columns, W % 16.
 int mmseg_conv3_norm_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                         int dtype) {
@@ -6142,7 +5620,7 @@ int mmseg_conv3_norm_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D
   g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
   g.D = D; g.H = H; g.W = W; g.ksplit = 1;
   g.out = reinterpret_cast<void*>(static_cast<uintptr_t>(256));   // the caller's output is 16-B aligned (checked)
-  return brick5_selected(g, 2) ? 1 : 0;
+  return brick6_selected(g, 2) ? 1 : 0;
 }
 
 // 3^3 conv forward of an A source holding the PRE-norm activation of an InstanceNorm + ReLU: the kernel stages
@@ -6156,7 +5634,7 @@ int mmseg_conv3_fwd_norm(const void* a, int lda, const float* nmean, const float
                 "conv3_fwd_norm: unsupported shape (mmseg_conv3_norm_ok)");
   const int KGp = (KG + 3) & ~3;
   GemmArgs g{a, lda, wpacked, bias, out, ldo, nullptr, M, Ncols, Cpad, KG, cpg_shift, D, H, W, 1, KGp,
-             1 /* XCD-aware block remap */, nullptr, 0, nmean, nrstd};
+             1 /* XCD-aware block remap */, 0, nmean, nrstd};
   return launch_gemm<bf16_t, MODE_CONV3>(g, (hipStream_t)stream);
 }
 
@@ -6166,7 +5644,7 @@ int mmseg_conv3_fp8_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D,
   g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
   g.D = D; g.H = H; g.W = W; g.ksplit = 1;
   g.out = reinterpret_cast<void*>(static_cast<uintptr_t>(256));
-  return brick5_selected(g, 2) ? 1 : 0;
+  return brick6_selected(g, 2) ? 1 : 0;
 }
 
 int mmseg_pack_conv3_fp8(const float* w, int Co, int Ci, int Cip, int KGp, int Cpad, void* dst, float* wdq,
@@ -6190,14 +5668,14 @@ int mmseg_conv3_fwd_fp8(const void* a, int lda, const float* nmean, const float*
                 "conv3_fwd_fp8: unsupported shape (mmseg_conv3_fp8_ok)");
   const int KGp = (KG + 3) & ~3;
   GemmArgs g{a, lda, w8, bias, out, ldo, nullptr, M, Ncols, Cpad, KG, cpg_shift, D, H, W, 1, KGp,
-             1 /* XCD-aware block remap */, nullptr, 0, nmean, nrstd};
+             1 /* XCD-aware block remap */, 0, nmean, nrstd};
   g.wdq = wdq;
-  launch_brick5(g, (hipStream_t)stream);
+  launch_brick6(g, (hipStream_t)stream);
   return mmseg::check_launch("conv3_fwd_fp8");
 }
 
 // Chunks per sample of the InstanceNorm-backward partials mmseg_conv3_dgrad_in writes for this CONV3 data-gradient
-// shape (the brick5 kernel's blocks per column tile), or 0 when that kernel does not run it.
+// shape (the brick6 kernel's blocks per column tile), or 0 when that kernel does not run it.
 int mmseg_conv3_dgrad_in_chunks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
                                 int ldo, int dtype) {
   if (dtype != MMSEG_BF16) return 0;
@@ -6205,15 +5683,15 @@ int mmseg_conv3_dgrad_in_chunks(int M, int Ncols, int Cpad, int KG, int cpg_shif
   g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
   g.D = D; g.H = H; g.W = W; g.ksplit = 1;
   g.out = reinterpret_cast<void*>(static_cast<uintptr_t>(256));   // the caller's output is 16-B aligned (checked)
-  if (!brick5_selected(g, 2)) return 0;
+  if (!brick6_selected(g, 2)) return 0;
   const int nt_n = Ncols / 32;
   const int per_nt = std::max(1, knob("MMSEG_BRICK4_BLOCKS", 256) / nt_n);
-  const int nb5 = (M / (D * H * W)) * (D / 4) * (H / 4) * (W / 16);
-  const int upb5 = ceil_div(nb5, std::min(per_nt, nb5));
-  return ceil_div(nb5, upb5);
+  const int nb6 = (M / (D * H * W)) * (D / 4) * (H / 4) * (W / 16);
+  const int upb6 = ceil_div(nb6, std::min(per_nt, nb6));
+  return ceil_div(nb6, upb6);
 }
 
-// CONV3 data gradient (mmseg_conv_gemm_ex, ksplit 1, no bias) whose output dy feeds the backward of an InstanceNorm +
+// CONV3 data gradient (mmseg_conv_gemm, ksplit 1, no bias) whose output dy feeds the backward of an InstanceNorm +
 // ReLU with pre-norm input inx (pitch ldinx) and statistics inmean / inrstd [N][Ncols]: the kernel also writes that
 // backward's partial sums inpart [N][mmseg_conv3_dgrad_in_chunks()][Ncols][2] (the layout mmseg_instnorm_bwd_part
 // reads), so its partial pass over x and dy is skipped.
@@ -6225,13 +5703,13 @@ int mmseg_conv3_dgrad_in(const void* a, int lda, const void* wpacked, void* out,
                 "conv3_dgrad_in: unsupported shape (mmseg_conv3_dgrad_in_chunks)");
   const int KGp = (KG + 3) & ~3;
   GemmArgs g{a, lda, wpacked, nullptr, out, ldo, nullptr, M, Ncols, Cpad, KG, cpg_shift, D, H, W, 1, KGp,
-             1 /* XCD-aware block remap */, nullptr, 0, nullptr, nullptr};
+             1 /* XCD-aware block remap */, 0, nullptr, nullptr};
   g.inx = inx;
   g.ldinx = ldinx;
   g.inmean = inmean;
   g.inrstd = inrstd;
   g.inpart = inpart;
-  launch_brick5(g, (hipStream_t)stream);
+  launch_brick6(g, (hipStream_t)stream);
   return mmseg::check_launch("conv3_dgrad_in");
 }
 
@@ -6259,13 +5737,6 @@ int mmseg_conv3_wgrad_group_ok(long long V, int Co, int Cip, int Ci, int cpg_shi
              ? 1 : 0;
 }
 // split count of a grouped conv (mmseg_conv_gemm_group): the runtime-brick plan's
-// Bricks per sample for which the grouped (forced runtime-brick) conv can emit fused InstanceNorm partials
-// (mmseg_conv_gemm_group_stats): none (see the function).
-int mmseg_conv3_group_stats_bricks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
-                                   int ldo, int dtype) {
-  return 0;   // (as mmseg_conv3_stats_bricks: equal per step, r04ad -- the epilogue costs what the pass did)
-}
-
 int mmseg_conv3_group_splits(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                              int dtype) {
   const Conv3Plan p = plan_conv3(M, Ncols, 8 << cpg_shift, D, H, W, lda, ldo, dtype == MMSEG_BF16 ? 2 : 4, true);

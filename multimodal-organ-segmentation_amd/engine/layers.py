@@ -318,40 +318,14 @@ class Conv3:
 
     def _stem(self, x: Act, y_ld: int) -> bool:
         """First conv on the packed input: K = 27*Ci real taps*channels (stem.hip).  The 48-output-channel stem is
-        SwinUNETR's bias-free encoder1 conv only: its weight gradient has no bias term, fused statistics or fused
-        norm backward, so a biased 48-channel first conv (a UNet3D / DualEncoder with features[0] = 48) takes the
-        implicit-GEMM path."""
+        SwinUNETR's bias-free encoder1 conv only: its weight gradient has no bias term or fused norm backward, so a
+        biased 48-channel first conv (a UNet3D / DualEncoder with features[0] = 48) takes the implicit-GEMM path."""
         if self.Co == 48 and self.conv.bias is not None:
             return False
         return (not self.need_dgrad and self.Cip == 8
                 and bool(self.rt.lib.mmseg_stem_ok(self.Ci, self.Co, x.D, x.H, x.W, x.ld, y_ld)))
 
-    def stats_bricks(self, x: Act, y: Act) -> int:
-        """Bricks per sample for which fwd() can emit fused InstanceNorm partials (0 = not available)."""
-        if self._stem(x, y.ld):
-            # the stem's epilogue can emit its output's statistics per 64-voxel slice, but that measured slower
-            # (stem +14.5 us and the slice merge 105 us per launch against a 20 + 5 us statistics pass, rocprofv3
-            # r02h): the statistics pass runs (mmseg_stem_fwd_stats stays in the ABI)
-            return 0
-        return self.rt.lib.mmseg_conv3_stats_bricks(x.N * x.V, self.Co, self.Cpad, self.KG, self.cpg_shift, x.D, x.H,
-                                                    x.W, x.ld, y.ld, self.rt.code)
-
-    def fwd(self, x: Act, y: Act, stats_part: Optional[torch.Tensor] = None):
-        if stats_part is not None and self._stem(x, y.ld):
-            with TIMER.region("stem_fwd_kernel", flops=2.0 * x.N * x.V * self.Co * 27 * self.Ci,
-                              nbytes=_io_bytes(self.rt, x.N * x.V, 8, self.Co, 27 * self.Ci * self.Co, 4)):
-                self.rt.lib.mmseg_stem_fwd_stats(x.ptr, x.ld, self.Ci, ptr(self.conv.weight), ptr(self.conv.bias),
-                                                 y.ptr, y.ld, x.N, x.D, x.H, x.W, self.Co, ptr(stats_part),
-                                                 self.rt.code, self.rt.stream)
-            return
-        if stats_part is not None:
-            with TIMER.region(_gemm_name(self.rt, self.Co, "conv3"), flops=2.0 * x.N * x.V * self.Co * 27 * self.Ci,
-                              nbytes=_io_bytes(self.rt, x.N * x.V, self.Ci, self.Co, 27 * self.Ci * self.Co)):
-                self.rt.lib.mmseg_conv_gemm_ex(x.ptr, x.ld, ptr(self.wf), ptr(self.conv.bias), y.ptr, y.ld, None,
-                                               MODE_CONV3, x.N * x.V, self.Co, self.Cpad, self.KG, self.cpg_shift,
-                                               x.D, x.H, x.W, 1, ptr(stats_part), self.kreal_f, self.rt.code,
-                                               self.rt.stream)
-            return
+    def fwd(self, x: Act, y: Act):
         if self._stem(x, y.ld):
             with TIMER.region("stem_fwd_kernel", flops=2.0 * x.N * x.V * self.Co * 27 * self.Ci,
                               nbytes=_io_bytes(self.rt, x.N * x.V, 8, self.Co, 27 * self.Ci * self.Co, 4)):
@@ -375,7 +349,7 @@ class Conv3:
 
     def norm_ok(self, x: Act, y: Act) -> bool:
         """True when this conv can take its input as the PRE-norm activation of an InstanceNorm + ReLU and apply
-        it on staging, forward and weight gradient (fwd_norm / bwd(norm=...)): the brick5 / brick2 kernels."""
+        it on staging, forward and weight gradient (fwd_norm / bwd(norm=...)): the brick6 / brick2 kernels."""
         L, code = self.rt.lib, self.rt.code
         return (self.need_dgrad and self.wg_stage is None and self.Cip == self.Ci and self.ncols_f == self.Co
                 and not self._stem(x, y.ld)
@@ -693,21 +667,15 @@ class Block:
         self.y1 = rt.act(N, D, H, W, C)
         self.x2 = rt.act(N, D, H, W, C)
         self.stats = torch.empty(4, N * C, dtype=torch.float32, device=rt.device)  # m1, r1, m2, r2
-        self.nb = None   # fused-statistics bricks per sample of (conv1, conv2), set on the first forward
         # conv1's InstanceNorm + ReLU applied by conv2's kernels on staging (y1 never written): the 96^3 32 -> 32
-        # layers (brick5 forward, brick2 weight gradient)
+        # layers (brick6 forward, brick2 weight gradient)
         self.norm1_ok = None
         self.defer1 = False
 
-    def _norm_fwd(self, x: Act, y: Act, m: torch.Tensor, r: torch.Tensor, part=None, nb: int = 0):
+    def _norm_fwd(self, x: Act, y: Act, m: torch.Tensor, r: torch.Tensor):
         L, s, code = self.rt.lib, self.rt.stream, self.rt.code
-        if part is not None:
-            L.mmseg_instnorm_stats_bricks(ptr(part), x.N, x.C, nb, x.V // nb, IN_EPS, ptr(m), x.C, ptr(r), s)
-            L.mmseg_instnorm_relu_fwd(x.ptr, x.ld, y.ptr, y.ld, x.N, x.V, x.C, ptr(m), ptr(r), code, s)
-        else:
-            ws = self.rt.ws(L.mmseg_instnorm_ws_floats(x.N, x.V, x.C))
-            L.mmseg_instnorm_fwd(x.ptr, x.ld, y.ptr, y.ld, x.N, x.V, x.C, IN_EPS, ptr(m), x.C, ptr(r), 1, ptr(ws),
-                                 code, s)
+        ws = self.rt.ws(L.mmseg_instnorm_ws_floats(x.N, x.V, x.C))
+        L.mmseg_instnorm_fwd(x.ptr, x.ld, y.ptr, y.ld, x.N, x.V, x.C, IN_EPS, ptr(m), x.C, ptr(r), 1, ptr(ws), code, s)
 
     def _norm_bwd(self, x: Act, m: torch.Tensor, r: torch.Tensor, dy: DySpec, dx: Act):
         L, s, code = self.rt.lib, self.rt.stream, self.rt.code
@@ -740,34 +708,25 @@ class Block:
     def fwd(self, xin: Act, out: Act):
         self.setup(xin.N, xin.D, xin.H, xin.W)
         st = self.stats
-        if self.nb is None:
-            self.nb = (self.c1.stats_bricks(xin, self.x1), self.c2.stats_bricks(self.y1, self.x2))
-            n = max(self.nb)
-            self.part = torch.empty(xin.N * n * self.Co * 2, dtype=torch.float32, device=self.rt.device) if n else None
-        p1 = self.part if self.nb[0] else None
-        p2 = self.part if self.nb[1] else None
         if self.norm1_ok is None:
-            self.norm1_ok = not self.nb[1] and self.c2.norm_ok(self.x1, self.x2)
+            self.norm1_ok = self.c2.norm_ok(self.x1, self.x2)
         self.defer1 = self.norm1_ok and os.environ.get("MMSEG_DEFER_CONV_NORM", "1") != "0"   # per forward (A/B)
-        self.c1.fwd(xin, self.x1, stats_part=p1)
+        self.c1.fwd(xin, self.x1)
         if self.defer1:
-            self._norm_stats(self.x1, st[0], st[1], p1, self.nb[0])
+            self._norm_stats(self.x1, st[0], st[1])
             self.c2.fwd_norm(self.x1, st[0], st[1], self.x2)
         else:
-            self._norm_fwd(self.x1, self.y1, st[0], st[1], p1, self.nb[0])
-            self.c2.fwd(self.y1, self.x2, stats_part=p2)
+            self._norm_fwd(self.x1, self.y1, st[0], st[1])
+            self.c2.fwd(self.y1, self.x2)
         if self.defer_out:
-            self._norm_stats(self.x2, st[2], st[3], p2, self.nb[1])
+            self._norm_stats(self.x2, st[2], st[3])
         else:
-            self._norm_fwd(self.x2, out, st[2], st[3], p2, self.nb[1])
+            self._norm_fwd(self.x2, out, st[2], st[3])
 
-    def _norm_stats(self, x: Act, m: torch.Tensor, r: torch.Tensor, part=None, nb: int = 0):
+    def _norm_stats(self, x: Act, m: torch.Tensor, r: torch.Tensor):
         L, s, code = self.rt.lib, self.rt.stream, self.rt.code
-        if part is not None:
-            L.mmseg_instnorm_stats_bricks(ptr(part), x.N, x.C, nb, x.V // nb, IN_EPS, ptr(m), x.C, ptr(r), s)
-        else:
-            ws = self.rt.ws(L.mmseg_instnorm_ws_floats(x.N, x.V, x.C))
-            L.mmseg_instnorm_stats(x.ptr, x.ld, x.N, x.V, x.C, IN_EPS, ptr(m), x.C, ptr(r), ptr(ws), code, s)
+        ws = self.rt.ws(L.mmseg_instnorm_ws_floats(x.N, x.V, x.C))
+        L.mmseg_instnorm_stats(x.ptr, x.ld, x.N, x.V, x.C, IN_EPS, ptr(m), x.C, ptr(r), ptr(ws), code, s)
 
     def out_stats(self):
         """(pre-norm x2, mean, rstd) of the block's output InstanceNorm (for consumers of a deferred output)."""
@@ -785,7 +744,7 @@ class Block:
         if not out_done:
             self._norm_bwd(self.x2, st[2], st[3], dy, g2)
         dy1 = self.y1                     # conv2 wgrad reads y1 before dgrad overwrites it
-        # conv2's data gradient may also sum conv1's InstanceNorm-backward partials (brick5 shapes)
+        # conv2's data gradient may also sum conv1's InstanceNorm-backward partials (brick6 shapes)
         inp = (self.x1, st[0], st[1])
         if self.defer1:                   # (y1 was never written: the weight gradient normalises x1 itself)
             part = self.c2.bwd(self.x1, g2, dy1, accumulate, norm=(st[0], st[1]), inp=inp)
@@ -858,22 +817,9 @@ class ConvGroup:
                 and bool(L.mmseg_conv3_wgrad_group_ok(M, c.Co, c.Cip, c.Ci, c.cpg_shift, x.D, x.H, x.W, y.ld, x.ld,
                                                       code)))
 
-    def stats_bricks(self, x: Act, y: Act) -> int:
-        """Bricks per sample for which fwd() can emit fused InstanceNorm partials (0 = not available)."""
-        c = self.c0
-        return self.rt.lib.mmseg_conv3_group_stats_bricks(x.N * x.V, c.ncols_f, c.Cpad, c.KG, c.cpg_shift, x.D, x.H,
-                                                          x.W, x.ld, y.ld, self.rt.code)
-
-    def fwd(self, x: Act, y: Act, stats_part: Optional[torch.Tensor] = None):
+    def fwd(self, x: Act, y: Act):
         c, L = self.c0, self.rt.lib
         M, nc = x.N * x.V, c.ncols_f
-        if stats_part is not None:
-            with TIMER.region(_gemm_name(self.rt, nc, "conv3"), flops=2.0 * M * c.Co * 27 * c.Ci,
-                              nbytes=_io_bytes(self.rt, M, c.Cip, c.Co, self.G * 27 * c.Cip * c.Co)):
-                L.mmseg_conv_gemm_group_stats(x.ptr, x.ld, ptr(c.wf), ptr(c.conv.bias), y.ptr, y.ld, MODE_CONV3, M, nc,
-                                              c.Cpad, c.KG, c.cpg_shift, x.D, x.H, x.W, c.kreal_f, self.G, self.w_gs,
-                                              self.b_gs, ptr(stats_part), self.rt.code, self.rt.stream)
-            return
         ks = L.mmseg_conv3_group_splits(M, nc, c.Cpad, c.KG, c.cpg_shift, x.D, x.H, x.W, x.ld, y.ld, self.rt.code)
         ws = self.rt.ws(ks * M * nc) if ks > 1 else None
         with TIMER.region(_gemm_name(self.rt, nc, "conv3"), flops=2.0 * M * c.Co * 27 * c.Ci,
@@ -957,12 +903,11 @@ class GroupBlock(Block):
         self.y1 = rt.act(G * N, D, H, W, C)
         self.x2 = rt.act(G * N, D, H, W, C)
         self.stats = torch.empty(4, G * N * C, dtype=torch.float32, device=rt.device)
-        self.gnb = None   # fused-statistics bricks per sample of (g1, g2), set on the first forward
         for g, b in enumerate(self.blocks):
             b.shape = (N, D, H, W)
             b.x1, b.y1, b.x2 = (act_group_view(t, g, N) for t in (self.x1, self.y1, self.x2))
             b.stats = self.stats[:, g * N * C:(g + 1) * N * C]
-            b.nb, b.norm1_ok, b.defer1, b.defer_out = (0, 0), False, False, False
+            b.norm1_ok, b.defer1, b.defer_out = False, False, False
 
     def ok(self, xin: Act) -> bool:
         # levels above the one-launch InstanceNorm size group with MMSEG_GROUP_FORCE_R (default on: the 24^3 / 48^3
@@ -972,21 +917,10 @@ class GroupBlock(Block):
 
     def fwd(self, xin: Act, out: Act):
         st = self.stats
-        if self.gnb is None:
-            # the statistics from the conv epilogue above the one-launch InstanceNorm size (48^3 / 24^3 with forced
-            # grouping); the register-resident small form needs no statistics pass to replace
-            big = self.x1.V > SMALL_IN_V
-            self.gnb = (self.g1.stats_bricks(xin, self.x1) if big else 0,
-                        self.g2.stats_bricks(self.y1, self.x2) if big else 0)
-            n = max(self.gnb)
-            self.gpart = (torch.empty(self.x1.N * n * self.Co * 2, dtype=torch.float32, device=self.rt.device)
-                          if n else None)
-        p1 = self.gpart if self.gnb[0] else None
-        p2 = self.gpart if self.gnb[1] else None
-        self.g1.fwd(xin, self.x1, stats_part=p1)
-        self._norm_fwd(self.x1, self.y1, st[0], st[1], p1, self.gnb[0])
-        self.g2.fwd(self.y1, self.x2, stats_part=p2)
-        self._norm_fwd(self.x2, out, st[2], st[3], p2, self.gnb[1])
+        self.g1.fwd(xin, self.x1)
+        self._norm_fwd(self.x1, self.y1, st[0], st[1])
+        self.g2.fwd(self.y1, self.x2)
+        self._norm_fwd(self.x2, out, st[2], st[3])
 
     def bwd(self, xin: Act, dy: DySpec, dxin: Optional[Act], accumulate: bool):
         st = self.stats

@@ -6,7 +6,7 @@ trainer.py:237-243).
 
 Cases: c2 UNet3D CT+PET 6 classes DiceCE; c3 DualEncoder "cross_attention" (= mean fusion, the bench
 workload) DiceCE; c5 DualEncoder CT+PET+MRI Tversky.  Each runs in fp32 (the parity path) and in bf16 (the path
-bench.py times: brick5 / brick3 / brick2-BN64 with 32-bit staging, wgrad_dma, the fused InstanceNorm partials,
+bench.py times: brick6 / brick3 / brick2-BN64 with 32-bit staging, wgrad_dma, the fused InstanceNorm partials,
 the fused head + loss), through Trainer._fused_loss exactly as Trainer.train_step does.
 
 Why the gradient bounds are relative to the reference's own rounding error: at 96^3 every weight gradient is a

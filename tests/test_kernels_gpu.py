@@ -61,12 +61,11 @@ def test_conv3_fwd_dgrad_wgrad(dev, dtype, cin, cout, shape):
     ({"MMSEG_BRICK4_BLOCKS": "3"}, 32, 32, (2, 8, 16, 8)),           # 8 bricks over 3 blocks, ragged ranges
     ({"MMSEG_BRICK4_BLOCKS": "4"}, 32, 64, (1, 4, 8, 16)),           # 2 column tiles x 2 blocks each
     ({}, 32, 32, (1, 12, 8, 24)),                                    # one brick per block, border bricks
-    # brick v5 (W % 16: 4x4x16 bricks, ky-shared A fragments)
+    # brick v6 (W % 16: 4x4x16 bricks, ky-shared A fragments, the staging interleaved between the MFMAs)
     ({"MMSEG_BRICK4_BLOCKS": "1"}, 32, 32, (2, 8, 16, 16)),          # one block over all 16 bricks of 2 samples
     ({"MMSEG_BRICK4_BLOCKS": "3"}, 32, 32, (2, 8, 8, 32)),           # 16 bricks over 3 blocks, ragged ranges
     ({}, 32, 32, (1, 12, 12, 16)),                                   # border bricks on every side
     ({"MMSEG_BRICK4_BLOCKS": "4"}, 32, 64, (1, 4, 4, 32)),           # 2 column tiles
-    # brick v6 (v5's register-staged path with the staging interleaved between the MFMAs)
     ({"MMSEG_BRICK4_BLOCKS": "1"}, 32, 32, (2, 4, 4, 16)),           # one brick per sample
     ({}, 128, 32, (1, 4, 16, 8)),                                   # BN32 ZW1, 4 input chunks
     ({}, 256, 128, (2, 12, 12, 12)),                                 # runtime brick (3,6,12) + chunk split-K
@@ -488,13 +487,6 @@ def test_batched_conv3_pack_matches_per_layer_pack(dev, dtype):
         assert torch.equal(wf.view(torch.int16) if dtype == torch.bfloat16 else wf, ref_f.view(torch.int16) if dtype == torch.bfloat16 else ref_f)
         if wd is not None:
             assert torch.equal(wd, l.wd)
-
-
-def test_conv3_fused_stats_not_offered(dev):
-    """The brick epilogues' fused InstanceNorm statistics measured no net gain (DESIGN round 2 / 4) and were removed
-    with their knobs in round 6: the library offers them for no shape, so the engine always runs the statistics
-    pass."""
-    assert lib().mmseg_conv3_stats_bricks(2 * 8 * 8 * 16, 32, 32, 27 * 4, 2, 8, 8, 16, 32, 32, 1) == 0
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

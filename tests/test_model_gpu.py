@@ -548,7 +548,7 @@ def test_deferred_conv_norm_bitwise(dev, model, wgrad_dma, monkeypatch):
 def test_head_in_partials(dev, model, dtype, knob, defer_head, monkeypatch):
     """32-channel top level: InstanceNorm-backward partial sums emitted by the producer of dy instead of a partial
     pass over x and dy -- by the fused head + loss backward for the last decoder block's output norm
-    (MMSEG_HEAD_IN_PART, mmseg_head_loss_bwd_in) and by conv2's brick5 data gradient for conv1's norm in every
+    (MMSEG_HEAD_IN_PART, mmseg_head_loss_bwd_in) and by conv2's brick6 data gradient for conv1's norm in every
     96^3-style block (MMSEG_DGRAD_IN_PART, mmseg_conv3_dgrad_in, bf16 only); both feed mmseg_instnorm_bwd_part.
     Same loss bits; gradients equal to the two-pass path (knob=0) up to the summation order of those partials
     (fp32 1e-5, bf16 1e-2 normwise: a bf16 activation rounding on the other side moves by one ulp); the head's own

@@ -3,10 +3,9 @@
     python tools/convbench.py [--shape N,S,Cin,Cout | N,D,H,W,Cin,Cout ...] [--iters 20] [--only fwd,dgrad,wgrad]
 Env knobs (MMSEG_*) select kernel variants; prints one JSON line per (shape, op) with
 the kernel the library launched, us per launch and TFLOP/s (2*27*Cin*Cout per voxel).
-Ops: fwd, fwds (forward with the fused InstanceNorm partials, as ConvBlock3D runs it), fwdn (forward of
-relu(IN(x)) with the norm applied on staging: Block.defer1's conv2), dgrad, dgradin (data gradient that also sums
-the InstanceNorm-backward partials of its output: Block.bwd's conv2 at 96^3), wgrad, wgradn (weight gradient with
-the deferred norm of x).
+Ops: fwd, fwdn (forward of relu(IN(x)) with the norm applied on staging: Block.defer1's conv2), dgrad, dgradin
+(data gradient that also sums the InstanceNorm-backward partials of its output: Block.bwd's conv2 at 96^3), wgrad,
+wgradn (weight gradient with the deferred norm of x).
 --probe: load libmmseg_hip_probe.so (make -C csrc probe) and print the block timeline of one launch per op
 (per-CU residency, block lifetimes, per-phase cycles of block 0's waves; see conv_gemm.hip PROBE_*).
 """
@@ -64,8 +63,6 @@ def main():
         flops = 2.0 * N * D * H * W * 27 * Ci * Co
         L, s, code = rt.lib, rt.stream, rt.code
 
-        nb = layer.stats_bricks(x, y)
-        part = torch.empty(N * max(nb, 1) * Co * 2, dtype=torch.float32, device=dev)
         mean = torch.zeros(N * Ci, dtype=torch.float32, device=dev)
         rstd = torch.ones(N * Ci, dtype=torch.float32, device=dev)
         inpart = torch.empty(N * 4096 * Ci * 2, dtype=torch.float32, device=dev)
@@ -73,9 +70,6 @@ def main():
         def run(op):
             if op == "fwd":
                 layer.fwd(x, y)
-            elif op == "fwds":
-                assert nb > 0, "no fused-statistics kernel for this shape (the library offers none since round 5)"
-                layer.fwd(x, y, stats_part=part)
             elif op == "fwdn":
                 layer.fwd_norm(x, mean, rstd, y)
             elif op == "dgradin":
