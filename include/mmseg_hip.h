@@ -564,6 +564,36 @@ int mmseg_dice_counts(const float* logits, const void* labels, int label_bytes, 
 /* counts from class-index masks (DiceMetric.update(pred, target), metrics.py:42-67). */
 int mmseg_dice_counts_idx(const void* pred, int pred_bytes, const void* labels, int label_bytes, long long total, int C,
                           unsigned long long* counts, void* stream);
+/* ------------------------------------------- boundary and confusion metrics */
+/* Masks are class-index volumes [B][H][W][D] (D contiguous), int64 or uint8 (*_bytes 8 / 1); foreground = value > 0.
+ * Every dim <= 32767, H*W*D < 2^30.
+ * mmseg_edt: exact Euclidean distance to the nearest foreground voxel of the same sample,
+ * scipy.ndimage.distance_transform_edt(~fg, sampling=(s0, s1, s2)) as called by HausdorffDistance.update
+ * (metrics.py:138-139) -> out [B][H][W][D] fp64; +inf throughout a sample without foreground.  A scan along D and
+ * two brute-force lower-envelope passes (W, H) that carry the winning integer offsets; the value is
+ * sqrt(((o0 s0)^2 + (o1 s1)^2) + (o2 s2)^2) in fp64, uncontracted.  ws: mmseg_edt_ws_bytes() bytes. */
+long long mmseg_edt_ws_bytes(int B, int H, int W, int D);
+int mmseg_edt(const void* mask, int mask_bytes, int B, int H, int W, int D, double s0, double s1, double s2,
+              double* out, void* ws, long long ws_bytes, void* stream);
+/* HausdorffDistance.update (metrics.py:110-152) up to the two order statistics of each sample: both distance
+ * transforms, the borders m ^ np.roll(m, 1, axis=0) (row 0 against row H-1), the distance-to-target at every pred
+ * border voxel and distance-to-pred at every target border voxel, and a radix select over their n fp64 bit
+ * patterns.  records [B][4] fp64 = {n, a[lo], a[hi], skipped}: a the sorted distances, lo = floor(vi),
+ * hi = min(lo + 1, n - 1), vi = (n - 1) * qfrac (numpy's "linear" virtual index, qfrac = percentile / 100);
+ * skipped = 1 when pred or target has no foreground or n == 0 (the reference appends nothing).
+ * ws: mmseg_hd_ws_bytes() bytes. */
+long long mmseg_hd_ws_bytes(int B, int H, int W, int D);
+int mmseg_hd_update(const void* pred, int pred_bytes, const void* target, int target_bytes, int B, int H, int W, int D,
+                    double s0, double s1, double s2, double qfrac, double* records, void* ws, long long ws_bytes,
+                    void* stream);
+/* ConfusionMatrix.update (metrics.py:184-196): counts[t * C + p] += 1 (int64, accumulates; C <= 16).  A pair with
+ * p or t outside [0, C) is counted in invalid[0] instead (the reference raises IndexError there).
+ * mmseg_confusion_counts: p = argmax over the C logits [N][C][V] (first maximum, NaN maximal, as
+ * mmseg_dice_counts). */
+int mmseg_confusion_counts_idx(const void* pred, int pred_bytes, const void* target, int target_bytes, long long total,
+                               int C, long long* counts, unsigned long long* invalid, void* stream);
+int mmseg_confusion_counts(const float* logits, const void* target, int target_bytes, int N, int C, long long V,
+                           long long* counts, unsigned long long* invalid, void* stream);
 /* AdamW step over flat fp32 buffers (torch.optim.AdamW op order, trainer.py:115-117).
  * skip (nullable): one device float, the step's count of out-of-range labels (mmseg_loss_fwd's last workspace
  * float, summed over the ranks under DP); when it is non-zero the kernel leaves p, m and v untouched, so a batch

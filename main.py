@@ -93,6 +93,13 @@ def run_eval(config, logger):
     trainer = Trainer(config=config, model=model, val_loader=get_dataloader(config, split="val"), logger=logger)
     metrics = trainer.evaluate()
     logger.info(f"Dice: {metrics['dice']:.4f} per class: {metrics['dice_per_class']}")
+    if "hausdorff_distance" in metrics:        # training.metrics lists hd95
+        logger.info(f"HD95: {metrics['hausdorff_distance']:.4f} +- {metrics.get('hausdorff_distance_std', 0.0):.4f}")
+    if "confusion_matrix" in metrics:          # training.metrics lists confusion
+        logger.info(f"Accuracy: {metrics['accuracy']:.4f} precision: {metrics['precision']:.4f} "
+                    f"recall: {metrics['recall']:.4f} F1: {metrics['f1']:.4f}")
+        logger.info(f"Precision per class: {metrics['precision_per_class']} recall per class: "
+                    f"{metrics['recall_per_class']}")
     return metrics
 
 

@@ -33,7 +33,7 @@ import torch.nn as nn
 from ..distributed import ddp
 from ..models.build import kernels_from_config, load_checkpoint, save_checkpoint
 from .losses import get_loss
-from .metrics import DiceMetric, get_metrics
+from .metrics import ConfusionMatrix, DiceMetric, HausdorffDistance, get_metrics, hd_from_moments
 from .optim import FlatAdamW, pack_source
 
 try:
@@ -378,10 +378,22 @@ class Trainer:
                 it.set_postfix({"loss": f"{lv:.4f}"})
         return total / n
 
+    def _extra_metrics(self) -> Tuple[Optional[HausdorffDistance], Optional[ConfusionMatrix]]:
+        """The metrics training.metrics lists besides Dice ("hd95": HausdorffDistance(95) of the foreground union at
+        unit spacing, "confusion": ConfusionMatrix).  Absent, or ["dice"]: none."""
+        want = self.config["training"].get("metrics") or ["dice"]
+        unknown = [m for m in want if m not in ("dice", "hd95", "confusion")]
+        if unknown:
+            raise ValueError(f"training.metrics: unknown metric(s) {unknown}; choose from dice, hd95, confusion")
+        C = self.config["model"]["out_channels"]
+        return (HausdorffDistance(95) if "hd95" in want else None,
+                ConfusionMatrix(num_classes=C) if "confusion" in want else None)
+
     def _validate(self) -> Tuple[float, Dict[str, float]]:
         self.check_deferred()
         self.model.eval()
         dm = DiceMetric(num_classes=self.config["model"]["out_channels"], device=self.device)
+        hd, cm = self._extra_metrics()
         total = torch.zeros((), dtype=torch.float64, device=self.device)
         n = 0
         with torch.no_grad():
@@ -390,7 +402,19 @@ class Trainer:
                 labels = batch["label"].to(self.device, non_blocking=True)
                 outputs = self.model(images)
                 total += self.criterion(outputs, labels).double()
-                dm.update_from_logits(outputs, labels)
+                if hd is None and cm is None:
+                    dm.update_from_logits(outputs, labels)
+                else:
+                    # the argmax mask the Dice kernel computes anyway (its pred_out) feeds the other metrics
+                    if labels.dtype not in (torch.int64, torch.uint8):
+                        labels = labels.long()
+                    labels = labels.contiguous()
+                    pred = torch.empty_like(labels)
+                    dm.update_from_logits(outputs, labels, pred_out=pred)
+                    if hd is not None:
+                        hd.update(pred, labels)
+                    if cm is not None:
+                        cm.update(pred, labels)
                 n += 1
         if self.world > 1:
             # one all-reduce of [loss sum, batch count, I, U]: the real per-rank batch counts are summed,
@@ -402,7 +426,22 @@ class Trainer:
             total = packed[0].double()
             n = int(round(packed[1].item()))
             dm.intersection, dm.union = packed[2:2 + C], packed[2 + C:]
-        return (total / n).item() if n else float("nan"), dm.compute()
+        results = dm.compute()
+        if hd is not None:
+            if self.world > 1:
+                # per-sample distances live on their ranks: [count, sum d, sum d^2] summed in fp64 (the std is
+                # then not bit-equal to np.std of the gathered list, see metrics.hd_from_moments)
+                mom = torch.from_numpy(hd.moments()).to(self.device)
+                ddp.allreduce_sum_(mom)
+                results.update(hd_from_moments(mom.cpu().numpy()))
+            else:
+                results.update(hd.compute())
+        if cm is not None:
+            if self.world > 1:
+                dev = cm._buffers(self.device)     # a rank with no batches contributes zeros
+                ddp.allreduce_sum_(dev)            # int64 SUM: matrix and invalid count stay exact
+            results.update(cm.compute())
+        return (total / n).item() if n else float("nan"), results
 
     def evaluate(self) -> Dict[str, float]:
         _, metrics = self._validate()
