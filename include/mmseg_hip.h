@@ -330,6 +330,13 @@ int mmseg_fuse_fwd(const void* const* srcs, const int* lds, int M, float wconst,
 int mmseg_fuse_norm_fwd(const void* const* srcs, const int* lds, const float* const* means, const float* const* rstds,
                         int M, float wconst, const float* wts, void* out, int ldo, int N, long long V, int C,
                         int dtype, void* stream);
+/* Mean / add fusion and the MaxPool3d(2) of every source as one pass over the sources (M = 2 or 3): out as
+ * mmseg_fuse_fwd (wts null) writes it, ys[m] / idxs[m] (pooled rows of ldys[m]; argmax [N][Vo][C]) as
+ * mmseg_maxpool2_fwd writes them for source m, all bitwise.  means / rstds given (M pointers to [N][C]): the
+ * sources are PRE-norm, as for mmseg_fuse_norm_fwd / mmseg_maxpool2_norm_fwd; both null: sources as stored. */
+int mmseg_fuse_pool_fwd(const void* const* srcs, const int* lds, const float* const* means, const float* const* rstds,
+                        int M, float wconst, void* out, int ldo, void* const* ys, const int* ldys,
+                        uint8_t* const* idxs, int N, int D, int H, int W, int C, int dtype, void* stream);
 /* CrossModalAttention gate: Linear -> ReLU -> Linear -> softmax (dual_encoder.py:226-233). */
 int mmseg_attn_gate_fwd(const float* pooled, const float* W1, const float* b1, const float* W2, const float* b2,
                         float* hbuf, float* wts, int N, int MC, int Hd, int M, void* stream);

@@ -1226,6 +1226,111 @@ __global__ void fuse_norm_fwd_m(FuseSrc s, T* __restrict__ out, int ldo, long lo
   }
 }
 
+// Mean / add fusion and the MaxPool of every source in ONE pass over the sources: an encoder level's output is
+// read by exactly these two consumers (fuse_norm_fwd_m / fuse_fwd and maxpool2_fwd per source), which ran as
+// separate launches and each fetched the level again from HBM.  One thread owns one pooled voxel and 8 channels
+// of one sample: it loads the window's 8 voxels of all MM sources (16-B loads, issued before use), writes the 8
+// fused voxels, and per source the pooled voxel and the argmax codes.
+// Same operations in the same order as the kernels it replaces, so every output is bitwise theirs: the value is
+// relu((x - mean) * rstd) rounded to T (NORM) or the source as stored, the fusion is acc = 0 + a_0 + a_1 .. times
+// wconst, and the pool takes the first maximum in z, y, x order (torch's rule: v > best or v is NaN replaces).
+struct FusePoolSrc {
+  const void* p[3];
+  int ld[3];
+  const float* mean[3];   // NORM: [N][C] per source
+  const float* rstd[3];
+  void* y[3];             // pooled [N][Vo] rows of ldy[m]
+  int ldy[3];
+  uint8_t* idx[3];        // argmax codes [N][Vo][C]
+  float wconst;
+};
+
+template <typename T, int MM, bool NORM>
+__global__ __launch_bounds__(256) void fuse_pool_fwd_m(FusePoolSrc s, T* __restrict__ out, int ldo, int N, int D,
+                                                       int H, int W, int C) {
+  const int C8 = C >> 3;
+  const int Do = D >> 1, Ho = H >> 1, Wo = W >> 1;
+  const int total = N * Do * Ho * Wo * C8;   // < 2^31 (host check)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int cg = i % C8;
+  int q = i / C8;
+  const int xo = q % Wo;
+  q /= Wo;
+  const int yo = q % Ho;
+  q /= Ho;
+  const int zo = q % Do;
+  const int n = q / Do;
+  const long long in0 = ((long long)(n * D + 2 * zo) * H + 2 * yo) * (long long)W + 2 * xo;
+  const long long vo = ((long long)(n * Do + zo) * Ho + yo) * Wo + xo;
+  // window voxels in flight at once: all 8 for 16-B vectors, fewer for fp32 (the registers of 8 x MM 32-B vectors
+  // would spill)
+  constexpr int TB = sizeof(T) == 2 ? 8 : (MM == 2 ? 4 : 2);
+  float mu[MM][8], rs[MM][8];
+  if constexpr (NORM) {
+#pragma unroll
+    for (int m = 0; m < MM; ++m) {
+      load8f(s.mean[m] + n * C + cg * 8, mu[m]);
+      load8f(s.rstd[m] + n * C + cg * 8, rs[m]);
+    }
+  }
+  float best[MM][8];
+  uint8_t bi[MM][8];
+#pragma unroll
+  for (int t0 = 0; t0 < 8; t0 += TB) {
+    V8<T> a[TB][MM];
+#pragma unroll
+    for (int u = 0; u < TB; ++u) {
+      const int t = t0 + u;
+      const long long vin = in0 + ((long long)(t >> 2) * H + ((t >> 1) & 1)) * W + (t & 1);
+#pragma unroll
+      for (int m = 0; m < MM; ++m) a[u][m].load(reinterpret_cast<const T*>(s.p[m]) + vin * s.ld[m] + cg * 8);
+    }
+#pragma unroll
+    for (int u = 0; u < TB; ++u) {
+      const int t = t0 + u;
+      const long long vin = in0 + ((long long)(t >> 2) * H + ((t >> 1) & 1)) * W + (t & 1);
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+      for (int m = 0; m < MM; ++m) {
+        if constexpr (NORM) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float h = (a[u][m].get(j) - mu[m][j]) * rs[m][j];
+            a[u][m].set(j, h > 0.f ? h : 0.f);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float v = a[u][m].get(j);
+          acc[j] = acc[j] + v;
+          if (t == 0 || v > best[m][j] || v != v) {
+            best[m][j] = v;
+            bi[m][j] = (uint8_t)t;
+          }
+        }
+      }
+      V8<T> o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o.set(j, acc[j] * s.wconst);
+      o.store(out + vin * ldo + cg * 8);
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    V8<T> o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.set(j, best[m][j]);
+    o.store(reinterpret_cast<T*>(s.y[m]) + vo * s.ldy[m] + cg * 8);
+    uint2 packed;
+    packed.x = bi[m][0] | (bi[m][1] << 8) | (bi[m][2] << 16) | ((uint32_t)bi[m][3] << 24);
+    packed.y = bi[m][4] | (bi[m][5] << 8) | (bi[m][6] << 16) | ((uint32_t)bi[m][7] << 24);
+    *reinterpret_cast<uint2*>(s.idx[m] + vo * C + cg * 8) = packed;
+  }
+}
+
 // dots[n][m] partial: sum_{v,c} dfused[n,v,c] * src_m[n,v,c]
 template <typename T>
 __global__ void fuse_dot_partial(FuseSrc s, const T* __restrict__ dfused, int ldd, long long V, int C, long long vpc,
@@ -1824,6 +1929,52 @@ int mmseg_fuse_fwd(const void* const* srcs, const int* lds, int M, float wconst,
   else
     MMSEG_LAUNCH(fuse_fwd<float>, dim3(grid), dim3(256), 0, st, s, (float*)out, ldo, V, N, C);
   return mmseg::check_launch("fuse_fwd");
+}
+
+// mmseg_fuse_fwd (wts null; means null) or mmseg_fuse_norm_fwd (means / rstds given) into `out`, and per source
+// mmseg_maxpool2_fwd / mmseg_maxpool2_norm_fwd into ys[m] / idxs[m], as one launch.
+int mmseg_fuse_pool_fwd(const void* const* srcs, const int* lds, const float* const* means, const float* const* rstds,
+                        int M, float wconst, void* out, int ldo, void* const* ys, const int* ldys,
+                        uint8_t* const* idxs, int N, int D, int H, int W, int C, int dtype, void* stream) {
+  MMSEG_REQUIRE((M == 2 || M == 3) && C % 8 == 0 && C > 0, "fuse_pool: M in {2, 3} and C%%8==0 required");
+  MMSEG_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && ((D | H | W) & 1) == 0, "fuse_pool: even dims required");
+  MMSEG_REQUIRE((means == nullptr) == (rstds == nullptr), "fuse_pool: means and rstds go together");
+  const long long total = (long long)N * (D / 2) * (H / 2) * (W / 2) * (C / 8);
+  // 32-bit item index, and n * D + z as an int in the kernel
+  MMSEG_REQUIRE(total <= kGridStrideMax && (long long)N * D < 2147483647LL, "fuse_pool: too many items");
+  FusePoolSrc s{};
+  for (int m = 0; m < M; ++m) {
+    MMSEG_REQUIRE(srcs[m] && ys[m] && idxs[m] && lds[m] >= C && ldys[m] >= C && lds[m] % 8 == 0 && ldys[m] % 8 == 0,
+                  "fuse_pool: source / pooled rows of at least C, multiples of 8");
+    s.p[m] = srcs[m];
+    s.ld[m] = lds[m];
+    if (means) {
+      MMSEG_REQUIRE(means[m] && rstds[m], "fuse_pool: statistics of every source");
+      s.mean[m] = means[m];
+      s.rstd[m] = rstds[m];
+    }
+    s.y[m] = ys[m];
+    s.ldy[m] = ldys[m];
+    s.idx[m] = idxs[m];
+  }
+  MMSEG_REQUIRE(out && ldo >= C && ldo % 8 == 0, "fuse_pool: output rows of at least C, a multiple of 8");
+  s.wconst = wconst;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = (int)((total + 255) / 256);
+  auto run = [&](auto tag) {
+    using T = decltype(tag);
+    if (M == 2 && means)
+      MMSEG_LAUNCH((fuse_pool_fwd_m<T, 2, true>), dim3(grid), dim3(256), 0, st, s, (T*)out, ldo, N, D, H, W, C);
+    else if (M == 2)
+      MMSEG_LAUNCH((fuse_pool_fwd_m<T, 2, false>), dim3(grid), dim3(256), 0, st, s, (T*)out, ldo, N, D, H, W, C);
+    else if (means)
+      MMSEG_LAUNCH((fuse_pool_fwd_m<T, 3, true>), dim3(grid), dim3(256), 0, st, s, (T*)out, ldo, N, D, H, W, C);
+    else
+      MMSEG_LAUNCH((fuse_pool_fwd_m<T, 3, false>), dim3(grid), dim3(256), 0, st, s, (T*)out, ldo, N, D, H, W, C);
+  };
+  if (dtype == MMSEG_BF16) run(bf16_t{});
+  else run(float{});
+  return mmseg::check_launch("fuse_pool_fwd");
 }
 
 int mmseg_attn_gate_fwd(const float* pooled, const float* W1, const float* b1, const float* W2, const float* b2,

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from .._lib import ptr
 from .layers import Block, ConvT2, DySpec, GroupBlock, Head, Packer, Point, act_group_view
+from .profiler import TIMER
 from .runtime import Act, FlatParams, Runtime
 
 
@@ -409,6 +410,53 @@ class DualEncoderProgram:
             else:
                 L.mmseg_fuse_fwd(srcs, lds, self.M, wconst, None, out.ptr, out.ld, N, V, C, code, s)
 
+    def _fuse_pool_fwd(self, l: int):
+        """Level l's fusion and every modality's maxpool into level l + 1 as one launch (mmseg_fuse_pool_fwd): the
+        level's outputs are read once instead of once by each of the two."""
+        L, s, code = self.rt.lib, self.rt.stream, self.rt.code
+        out = self.fused_out(l)
+        M = self.M
+        blks = [self.encs[m][l] for m in range(M)]
+        # a grouped level's block always materialises its output (GroupBlock.fwd); above them a deferred output
+        # exists only as the pre-norm x2 and its statistics
+        if l < self.l0 and blks[0].defer_out:
+            st = [b.out_stats() for b in blks]
+            srcs = [t[0] for t in st]
+            means = _ptr_array([t[1].data_ptr() for t in st])
+            rstds = _ptr_array([t[2].data_ptr() for t in st])
+        else:
+            srcs = [self.y[m][l] for m in range(M)]
+            means = rstds = None
+        pooled = [self.pooled[m][l + 1] for m in range(M)]
+        wconst = 1.0 if self.fusion == "add" else 1.0 / M
+        es = self.rt.dtype.itemsize
+        nvox = out.N * out.V
+        with TIMER.region("fuse_pool_fwd_m",
+                          nbytes=float(es * out.C * (M * nvox + nvox + M * nvox // 8) + M * out.C * nvox // 8)):
+            L.mmseg_fuse_pool_fwd(_ptr_array([a.ptr for a in srcs]), _int_array([a.ld for a in srcs]), means, rstds,
+                                  M, wconst, out.ptr, out.ld, _ptr_array([p.ptr for p in pooled]),
+                                  _int_array([p.ld for p in pooled]),
+                                  _ptr_array([ptr(self.idx[m][l + 1]) for m in range(M)]),
+                                  out.N, *self.dims[l], out.C, code, s)
+
+    def _fwd_fuse_pool(self, x: torch.Tensor):
+        """The encoders level by level (mean / add fusion): every modality's block of a level (one grouped launch
+        sequence at the grouped levels), then the level's fusion + maxpool pass."""
+        for l in range(self.L):
+            if l >= self.l0:
+                self.gblocks[l].fwd(self.pooled_g[l], self.y_g[l])
+            else:
+                for m in range(self.M):
+                    if l == 0:
+                        self.xin_v[m] = _pack_input(self.rt, self.encs[m][0], x, m, 1, self.xin[m])
+                        self.encs[m][0].fwd(self.xin_v[m], self.y[m][0])
+                    else:
+                        self.encs[m][l].fwd(self.pooled[m][l], self.y[m][l])
+            if l < self.L - 1:
+                self._fuse_pool_fwd(l)
+            else:
+                self._fuse_fwd(l)
+
     def materialize_features(self):
         """Write the encoder outputs the forward left deferred (return_features reads them)."""
         for m in range(self.M):
@@ -493,6 +541,13 @@ class DualEncoderProgram:
             for l in range(self.L):
                 d = self.dims[l]
                 self.encs[m][l].defer_out = defer and d[0] * d[1] * d[2] > SMALL_IN_V
+        # mean / add fusion: a level's fusion and its maxpools read the same tensors, so they run as one pass
+        # (MMSEG_FUSE_POOL=0: the separate launches, which a bitwise test compares against)
+        self.fuse_pool = (self.fusion in ("mean", "add") and self.M in (2, 3) and not self.multistream
+                          and os.environ.get("MMSEG_FUSE_POOL", "1") != "0")
+        if self.fuse_pool:
+            self._fwd_fuse_pool(x)
+            return self.dec.fwd(self.bottom, training, loss)
         streams = self._streams()
         split = min(max(self.stream_level, 0), self.L)
         if self.l0 < self.L:
