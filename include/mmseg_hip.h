@@ -485,6 +485,23 @@ int mmseg_augment(const float* src, int C, int D, int H, int W, const void* labe
                   int rot_k, const float* scale, const float* shift, int noise, double noise_mean, float noise_sd,
                   const unsigned long long* noise_key, float* dst, void* label_dst, void* stream);
 
+/* ------------------------------------------------------------ NIfTI volumes */
+/* The voxel block of a NIfTI-1 file decoded on the device (replaces load_nifti's get_fdata().astype and the
+ * np.stack(...).copy() of dataset.py:95-113): raw = X*Y*Z elements exactly as the file holds them (x fastest;
+ * datatype 2 uint8, 4 int16, 8 int32, 16 float32, 64 float64, 256 int8, 512 uint16, 768 uint32; swap != 0: the
+ * file's byte order is not the device's) -> out [X][Y][Z] fp32, z fastest.  Per element: unswap, to double, if
+ * scale `* slope` then `+ inter` as two rounded double operations, to float: bitwise numpy's
+ * (raw.astype(f8) * slope + inter).astype(f4).  raw is aligned to its element size and is not modified. */
+int mmseg_nifti_decode(const void* raw, int datatype, int swap, int X, int Y, int Z, int scale, double slope,
+                       double inter, float* out, void* stream);
+/* Same read side; the double is truncated toward zero and stored as int64 (label_bytes 8) or as the low byte of
+ * that int64 (label_bytes 1): load_nifti(path, dtype=np.int64) of dataset.py:105. */
+int mmseg_nifti_decode_label(const void* raw, int datatype, int swap, int X, int Y, int Z, int scale, double slope,
+                             double inter, void* out, int label_bytes, void* stream);
+/* torch.argmax over the classes of one volume's logits [C][X][Y][Z] fp32 (first maximum, a NaN counts as the
+ * maximum; C <= 255), written as uint8 in NIfTI file order: out[(z*Y + y)*X + x]  (trainer.py:364-368). */
+int mmseg_argmax_encode(const float* logits, int C, int X, int Y, int Z, unsigned char* out, void* stream);
+
 /* ------------------------------------------------ sliding-window inference */
 /* MONAI sliding_window_inference (constant blending) as called by Trainer._sliding_window_inference
  * (trainer.py:370-395).  win: device int[4*nw] = (n, z0, y0, x0) per window in the volume's frame

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Entry point mirroring the reference's `main.py --mode train|eval` (main.py:41-339, 501-549)
-on the MI355X engine.  Other modes (inference over NIfTI, preprocess, analysis)
-are outside the engine's scope and exit with a message.
+"""Entry point mirroring the reference's `main.py --mode train|eval|inference` (main.py:41-409, 501-549)
+on the MI355X engine.  Other modes (preprocess, analysis) are outside the engine's scope and exit
+with a message.
 
     python main.py --mode train --config configs/c2_unet_96_bf16.yaml
+    python main.py --mode inference --config configs/c6_unet_nifti.yaml --checkpoint outputs/c6_unet_nifti/best.pth \
+        --input data/new_cases --output outputs/predictions
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode train \
         --config configs/c3_dual_encoder_96_dp.yaml
 """
@@ -90,7 +92,9 @@ def run_eval(config, logger):
     model = build_model(config)
     if config["_args"].get("checkpoint"):
         load_checkpoint(model, config["_args"]["checkpoint"])
-    trainer = Trainer(config=config, model=model, val_loader=get_dataloader(config, split="val"), logger=logger)
+    # the reference's run_eval scores the test split (main.py:356); a config without a test_csv keeps the val split
+    split = "test" if config["data"].get("synthetic") is None and config["data"].get("test_csv") else "val"
+    trainer = Trainer(config=config, model=model, val_loader=get_dataloader(config, split=split), logger=logger)
     metrics = trainer.evaluate()
     logger.info(f"Dice: {metrics['dice']:.4f} per class: {metrics['dice_per_class']}")
     if "hausdorff_distance" in metrics:        # training.metrics lists hd95
@@ -101,6 +105,21 @@ def run_eval(config, logger):
         logger.info(f"Precision per class: {metrics['precision_per_class']} recall per class: "
                     f"{metrics['recall_per_class']}")
     return metrics
+
+
+def run_inference(config, logger):
+    """reference main.py:377-409: a checkpoint over a folder of NIfTI volumes (Trainer.predict)."""
+    from mmseg_amd.models.build import load_checkpoint
+    checkpoint, input_path = config["_args"].get("checkpoint"), config["_args"].get("input")
+    output_path = config["_args"].get("output") or "outputs/predictions"
+    if checkpoint is None:
+        raise ValueError("--checkpoint is required for inference mode")
+    if input_path is None:
+        raise ValueError("--input is required for inference mode")
+    logger.info(f"Input: {input_path}  Output: {output_path}")
+    model = build_model(config)
+    load_checkpoint(model, checkpoint)
+    Trainer(config=config, model=model, logger=logger).predict(input_path=input_path, output_path=output_path)
 
 
 def main(argv=None):
@@ -120,6 +139,9 @@ def main(argv=None):
         logger.info("Training completed")
     elif args.mode == "eval":
         run_eval(config, logger)
+    elif args.mode == "inference":
+        run_inference(config, logger)
+        logger.info("Inference completed")
     else:
         logger.error(f"--mode {args.mode} is outside the MI355X engine's scope (DESIGN.md 'Out of scope')")
         sys.exit(2)

@@ -1,8 +1,9 @@
 """get_dataloader(config, split) — reference src/data/dataloader.py:14-60.
 
-The reference reads a CSV of NIfTI files (nibabel, absent here); the engine's
-loader serves the seeded synthetic phantoms of data/synthetic.py in the same
-batch format.  Under data parallelism each rank takes samples r, r+W, ...
+Without data.synthetic the loader reads the reference's CSV lists of NIfTI files
+(data_root/{train_csv, val_csv, test_csv}) and decodes, normalises, augments and
+resizes them on the GPU (data/nifti.py).  With data.synthetic it serves the seeded
+phantoms of data/synthetic.py in the same batch format.  Under data parallelism each rank takes samples r, r+W, ...
 (DistributedSampler semantics).  With data.synthetic.device: true
 the phantoms are generated and normalised on the GPU instead (data/device.py), and
 data.augmentation.enabled: true augments the training split there (data/augment.py)."""
@@ -18,8 +19,13 @@ from .synthetic import SyntheticSegDataset
 def get_dataset(config: Dict[str, Any], split: str = "train"):
     syn = config["data"].get("synthetic")
     if syn is None:
-        raise NotImplementedError("NIfTI/CSV datasets are outside the engine's scope (nibabel is not available); "
-                                  "set data.synthetic: {n_train, n_val, size, seed}")
+        # data_root/{train,val,test}_csv of NIfTI files, decoded and transformed on the GPU (data/nifti.py);
+        # no GPU is touched before the first sample is fetched
+        from .augment import DeviceAugment
+        from .nifti import DeviceNiftiDataset, read_data_list
+        aug_cfg = config["data"].get("augmentation") or {}
+        augment = DeviceAugment(aug_cfg) if split == "train" and aug_cfg.get("enabled", False) else None
+        return DeviceNiftiDataset(config, read_data_list(config, split), mode=split, augment=augment)
     n = syn["n_train"] if split == "train" else syn.get("n_val", 2)
     seed = syn.get("seed", 1234) + (0 if split == "train" else 100000)
     return SyntheticSegDataset(n, syn.get("size", 96), config["model"]["out_channels"], config["data"]["modalities"],
@@ -27,6 +33,13 @@ def get_dataset(config: Dict[str, Any], split: str = "train"):
 
 
 def get_dataloader(config: Dict[str, Any], split: str = "train", shuffle=None, drop_last=None):
+    if config["data"].get("synthetic") is None:
+        from .device import DeviceLoader
+        ds = get_dataset(config, split)
+        return DeviceLoader(ds, config["training"]["batch_size"],
+                            shuffle=split == "train" if shuffle is None else shuffle,
+                            drop_last=split == "train" if drop_last is None else drop_last, seed=ds.seed,
+                            pad=split == "train")
     syn = config["data"].get("synthetic") or {}
     aug_cfg = config["data"].get("augmentation") or {}
     augment = split == "train" and aug_cfg.get("enabled", False)    # get_transforms: the train pipeline only

@@ -176,9 +176,10 @@ class DevicePhantomDataset:
 
 
 class DeviceLoader:
-    """Batches of a DevicePhantomDataset (DistributedSampler semantics under DP: rank r takes r, r+W, ...)."""
+    """Batches of a DevicePhantomDataset or a DeviceNiftiDataset (data/nifti.py): anything with get(i, epoch),
+    __len__ and mods (DistributedSampler semantics under DP: rank r takes r, r+W, ...)."""
 
-    def __init__(self, ds: DevicePhantomDataset, batch_size: int, shuffle: bool = False, drop_last: bool = False,
+    def __init__(self, ds, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 0, pad: bool = True):
         self.ds, self.B, self.shuffle, self.drop_last, self.seed = ds, batch_size, shuffle, drop_last, seed
         self.epoch = 0

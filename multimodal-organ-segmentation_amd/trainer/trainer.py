@@ -478,9 +478,36 @@ class Trainer:
                 break
         return self.history
 
-    def predict(self, input_path, output_path) -> None:  # pragma: no cover - NIfTI I/O is out of scope
-        raise NotImplementedError("inference over NIfTI folders is outside the engine's scope (SURVEY §8f rank 2); "
-                                  "volumes already in memory go through _sliding_window_inference")
+    def predict(self, input_path, output_path) -> None:
+        """reference trainer.py:303-368: every case under input_path/<modality.lower()>/<case>.nii[.gz] that has
+        all the modalities -> output_path/<case>_pred.nii.gz (uint8 class mask, the first modality's affine).
+        The volumes are decoded on the device, the windows run there, and the argmax is fused with the
+        permutation back to file order (mmseg_argmax_encode), so X*Y*Z bytes per case return to the host.
+        Like the reference, the windows see the RAW volume -- training normalises, this does not (DESIGN.md
+        "Semantics traps"); inference.normalize: true applies DeviceModalityNormalize first.  Under data
+        parallelism rank 0 predicts."""
+        if self.rank != 0:
+            return
+        from ..data.device import DeviceModalityNormalize
+        from ..data.nifti import HostStager, argmax_encode, find_cases, load_modalities
+        from ..utils.nifti import save_nifti
+        self.model.eval()
+        input_path, output_path = Path(input_path), Path(output_path)
+        output_path.mkdir(parents=True, exist_ok=True)
+        norm = (DeviceModalityNormalize(self.config) if self.config.get("inference", {}).get("normalize", False)
+                else None)
+        stager = HostStager(self.device)
+        cases = find_cases(input_path, self.config["data"]["modalities"])
+        with torch.no_grad():
+            for case_id, paths in tqdm(cases, desc="Inference"):
+                image, first = load_modalities(paths, stager)
+                if norm is not None:
+                    norm(image)
+                logits = self._sliding_window_inference(image.unsqueeze(0))
+                mask = argmax_encode(logits[0].float()).cpu().numpy().reshape(first.shape, order="F")
+                save_nifti(mask, output_path / f"{case_id}_pred.nii.gz", first.affine)
+                if self.logger:
+                    self.logger.info(f"Predicted {case_id}: {tuple(first.shape)} -> {case_id}_pred.nii.gz")
 
     def _sliding_window_inference(self, image: torch.Tensor) -> torch.Tensor:
         """reference trainer.py:370-395: MONAI sliding_window_inference(image, roi_size, sw_batch_size=
