@@ -86,6 +86,19 @@ int mmseg_conv3_dgrad_in(const void* a, int lda, const void* wpacked, void* out,
  * allocates ksplit*M*Ncols fp32 of split-K workspace and passes ksplit to mmseg_conv_gemm. */
 int mmseg_conv3_splits(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                        int dtype);
+/* Which kernel a 3^3 conv would take, without a GPU (value-returning): exactly the family name mmseg_last_kernel()
+ * gives after the launch.  Both assume 16-B aligned, unsplit outputs (no out2).
+ * mmseg_conv3_kernel: the forward / data gradient of the sibling queries' shape with cin_real real input channels
+ * (0 = all, as mmseg_conv_gemm_zw) and split count ksplit.  mmseg_conv3_wgrad_kernel: the weight gradient of
+ * mmseg_conv3_wgrad_ws_floats' shape with a workspace of ws_floats.
+ * flags: 1 deferred norm (mmseg_conv3_fwd_norm / _wgrad_norm), 2 IN-backward partials (mmseg_conv3_dgrad_in),
+ * 4 e4m3 weights (mmseg_conv3_fwd_fp8), 8 grouped (mmseg_conv_gemm_group / mmseg_conv3_wgrad_group, any group
+ * count), 16 last 16 rows padding (mmseg_conv3_wgrad_ex phase bit 8).  A flag the shape's kernel cannot serve
+ * gives the name of the kernel that would refuse it. */
+const char* mmseg_conv3_kernel(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
+                               int ldo, int cin_real, int ksplit, int flags, int dtype);
+const char* mmseg_conv3_wgrad_kernel(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W,
+                                     int lddy, int ldx, long long ws_floats, int flags, int dtype);
 /* Implicit-GEMM forward / data-gradient convolution on MFMA.
  * Replaces aten::convolution (fwd) and convolution_backward (grad_input) of
  * Conv3d(k3,p1) unet.py:26-27, ConvTranspose3d(k2,s2) unet.py:95, and the
@@ -126,16 +139,15 @@ int mmseg_conv_gemm_zw(const void* a, int lda, const void* wpacked, const float*
                        float* splitk_ws, int mode, int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H,
                        int W, int ksplit, int cin_real, int zcols, int dtype, void* stream);
 
-/* Weight-gradient partials part[ksplit][Ca][Ncols] (fp32), K = voxels.
- * Replaces convolution_backward (grad_weight) of the same layers; with
+/* Weight-gradient partials part[ksplit][Ca][Ncols] (fp32), K = voxels, of the 1x1 (mode 1) and transposed-conv
+ * (mode 3) layers; mode 0 is an error: the 3^3 weight gradient is mmseg_conv3_wgrad.
+ * Replaces convolution_backward (grad_weight) of those layers; with
  * bias_part != NULL (a = dy) also the grad_bias partials bias_part[ksplit][Ca]. */
 int mmseg_wgrad(const void* a, int lda, const void* b, int ldb, float* part, float* bias_part, int mode, int Ca,
                 int Ncols, int cpg_shift, long long V, int D, int H, int W, int ksplit, int dtype, void* stream);
-/* Split counts mmseg_wgrad will use (value-returning): callers size part[] with them.  For CONV3 the
- * library picks the split of its brick kernels itself; ksplit is then only the caller's workspace cap. */
+/* Split count mmseg_wgrad will use for a wanted ksplit (value-returning): the voxels in ranges of whole 64-voxel
+ * steps; callers size part[] with it. */
 int mmseg_wgrad_splits(long long V, int ksplit);
-int mmseg_wgrad_splits_conv3(long long V, int ksplit, int Ca, int cpg_shift, int D, int H, int W, int lda, int ldb,
-                             int dtype);
 /* Fixed-order sum of the partials into the torch-layout fp32 gradient. */
 int mmseg_wgrad_reduce(const float* part, float* grad, const float* bias_part, float* bias_grad, int Ca, int Ncols,
                        int ksplit, int cpad, int creal, int ntap, int accumulate, void* stream);

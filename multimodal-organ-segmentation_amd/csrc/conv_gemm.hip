@@ -2032,93 +2032,257 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
   }
 }
 
-// Host-side choice of the CONV3 kernel (shared by the launcher and mmseg_conv3_splits).
-struct Conv3Plan {
-  int kind;          // 0 per-lane gather GEMM, 1 brick2, 2 runtime brick
-  int bz, by, bx;    // kind 2
-  int ks;            // splits the plan wants (kind 2: over 32-channel chunks)
-  int bn;            // kind 2 column tile
+// ---- the kernel choice of a forward / data-gradient GEMM launch.  choose_gemm is the only place that decides it:
+// launch_gemm launches what it returns, and the planning queries (mmseg_conv3_splits, _group_ok, _norm_ok,
+// _fp8_ok, _dgrad_in_chunks, mmseg_conv3_kernel) answer from it without a GPU.
+enum GemmKernel {
+  GK_BRICKR,   // conv3_brickr_kernel: runtime brick (small volumes, grouped launches), splits over 32-channel chunks
+  GK_BRICK8,   // conv3_brick8_kernel: 8-wave 8x8x8 brick, LDS-DMA staging
+  GK_BRICK2_BN48, GK_BRICK2,   // conv3_brick2_kernel: 4x8x8 brick, 48-column tiles; 64 / 32-column tiles
+  GK_BRICK6,   // conv3_brick6_kernel: W % 16, one input chunk, 32 columns (deferred norm, e4m3, IN-backward partials)
+  GK_BRICK4,   // conv3_brick4_kernel: one input chunk, 32 columns, persistent
+  GK_BRICK3,   // conv3_brick3_kernel: 32-column tiles, persistent
+  GK_BRICK1,   // conv3_brick_kernel: the first brick generation (MMSEG_BRICK=1)
+  GK_GEMM_64x256, GK_GEMM_64x192, GK_GEMM_64x128, GK_GEMM_128x48, GK_GEMM_128x96, GK_GEMM_128x32, GK_GEMM_128x64
+};
+struct GemmChoice {
+  int kernel;          // GemmKernel
+  const char* name;    // the family noted for mmseg_last_kernel() / the per-kernel timer
+  int bn;              // column tile
+  int grid, block;
+  int upb, bpn;        // persistent kernels (brick6 / brick4 / brick3): units per block, blocks per column tile
+  int bz, by, bx;      // GK_BRICKR: the brick
+  bool b32, kw2;       // 32-bit offset halo staging; GK_BRICKR: two waves per SIMD over an in-block chunk split
+  int ksplit;          // the launch's split count (GK_BRICKR: clamped to whole chunk ranges)
+  bool reduce;         // a split-K reduce follows
+  int ks_want;         // CONV3: the split count this shape wants (mmseg_conv3_splits)
 };
 
-// force_r: the runtime-brick kernel even where the (4, 8, 8)-brick family fits -- the modality-grouped launches,
-// whose per-group weights only the runtime-brick kernel reads (24^3 with MMSEG_GROUP_FORCE_R)
-Conv3Plan plan_conv3(int M, int Ncols, int cin, int D, int H, int W, int lda, int ldo, int tsize,
-                     bool force_r = false) {
-  Conv3Plan p{0, 0, 0, 0, 1, 32};
-  bool k1_ok = false;   // the brick2 family can take the shape (used when the runtime brick cannot)
-  const int brick = knob("MMSEG_BRICK", 2);
-  const bool base_ok = cin % CK == 0 && lda % 8 == 0 && ldo % 8 == 0 && Ncols % 32 == 0;
-  // 48-column multiples (SwinUNETR's feature_size 48) run the brick2 kernel with 48-column tiles
-  const bool ok48 = cin % CK == 0 && lda % 8 == 0 && ldo % 8 == 0 && Ncols % 48 == 0;
-  if (!force_r && brick == 2 && (base_ok || ok48) && D % 4 == 0 && H % B2_Y == 0 && W % B2_X == 0) {
+// tsize: element bytes.  A grouped launch (g.grp_n > 0) takes the runtime-brick kernel even where the (4, 8, 8)-brick
+// family fits: only it reads per-group weights (24^3 with MMSEG_GROUP_FORCE_R).  A deferred norm, IN-backward
+// partials or e4m3 weights (g.nmean / g.inpart / g.wdq) are served by brick6 alone; the caller checks it got it.
+GemmChoice choose_gemm(const GemmArgs& g, int mode, int tsize) {
+  GemmChoice c{};
+  c.block = 256;
+  c.ksplit = g.ksplit;
+  c.ks_want = 1;
+  const bool bf16 = tsize == 2;
+  if (mode == MODE_CONV3) {
+    const int cin = 8 << g.cpg_shift, N = g.M / (g.D * g.H * g.W);
+    const int brick = knob("MMSEG_BRICK", 2);
+    const bool base_ok = cin % CK == 0 && g.lda % 8 == 0 && g.ldo % 8 == 0 && g.Ncols % 32 == 0;
+    // 48-column multiples (SwinUNETR's feature_size 48) run the brick2 kernel with 48-column tiles
+    const bool ok48 = cin % CK == 0 && g.lda % 8 == 0 && g.ldo % 8 == 0 && g.Ncols % 48 == 0;
+    const bool out16 = g.ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0;   // 16-B output stores
+    // 32-bit byte offsets into A; with them bf16 takes 32-bit offset halo staging (MMSEG_B32=0: the 64-bit staging)
+    const bool a31 = (long long)g.M * g.lda * tsize < (1LL << 31);
+    c.b32 = bf16 && knob("MMSEG_B32", 1) && a31;
+    const int nb1 = N * (g.D / 4) * (g.H / B2_Y) * (g.W / B2_X);   // 4x8x8 bricks
+    const bool fam = g.grp_n == 0 && brick == 2 && (base_ok || ok48) && g.D % 4 == 0 && g.H % B2_Y == 0 &&
+                     g.W % B2_X == 0;
     // a brick2-family launch has one block per (4x8x8 brick, column tile): at SwinUNETR's 8^3 / 16^3 levels
     // (384 / 192 channels) that is 12-48 blocks for the whole chip (brick3 at 75-290 TF/s, r05m).  Below
     // MMSEG_BRICK2_MINUNITS such shapes take the runtime-brick kernel, whose chunk splits fill the CUs.
-    const long long units = (long long)(M / (D * H * W)) * (D / 4) * (H / B2_Y) * (W / B2_X) *
-                            ((Ncols + 63) / 64);
-    if (!(base_ok && units < knob("MMSEG_BRICK2_MINUNITS", 128))) {
-      p.kind = 1;
-      return p;
-    }
-    k1_ok = true;
-  }
-  if (brick >= 2 && base_ok) {
-    int best = 0;
-    for (int bz = 1; bz <= D && bz <= 8; ++bz) {
-      if (D % bz) continue;
-      for (int by = 1; by <= H && by <= 16; ++by) {
-        if (H % by) continue;
-        for (int bx = 1; bx <= W && bx <= 16; ++bx) {
-          if (W % bx) continue;
-          const int rows = bz * by * bx;
-          const int halo = (bz + 2) * (by + 2) * (bx + 2);
-          const int hq = (bz + 2) * (by + 2) * ((bx + 2) * 2 * tsize + 2);
-          if (rows > 256 || halo > BR_MAXHV || hq > br_xq(tsize)) continue;
-          const int score = rows * 4 + (bx % 8 == 0 ? 2 : 0) + (by % 8 == 0 ? 1 : 0);
-          // ties go to the smaller halo (12^3: 6x6x6, 512 halo voxels and the compile-time kernel, over 3x6x12)
-          const bool tie_better = score == best && halo < (p.bz + 2) * (p.by + 2) * (p.bx + 2);
-          if (score > best || tie_better) {
-            best = score;
-            p.bz = bz; p.by = by; p.bx = bx;
+    const bool few = fam && base_ok && (long long)nb1 * ((g.Ncols + 63) / 64) < knob("MMSEG_BRICK2_MINUNITS", 128);
+    if ((!fam || few) && brick >= 2 && base_ok) {
+      int best = 0;
+      for (int bz = 1; bz <= g.D && bz <= 8; ++bz) {
+        if (g.D % bz) continue;
+        for (int by = 1; by <= g.H && by <= 16; ++by) {
+          if (g.H % by) continue;
+          for (int bx = 1; bx <= g.W && bx <= 16; ++bx) {
+            if (g.W % bx) continue;
+            const int rows = bz * by * bx;
+            const int halo = (bz + 2) * (by + 2) * (bx + 2);
+            const int hq = (bz + 2) * (by + 2) * ((bx + 2) * 2 * tsize + 2);
+            if (rows > 256 || halo > BR_MAXHV || hq > br_xq(tsize)) continue;
+            const int score = rows * 4 + (bx % 8 == 0 ? 2 : 0) + (by % 8 == 0 ? 1 : 0);
+            // ties go to the smaller halo (12^3: 6x6x6, 512 halo voxels and the compile-time kernel, over 3x6x12)
+            const bool tie_better = score == best && halo < (c.bz + 2) * (c.by + 2) * (c.bx + 2);
+            if (score > best || tie_better) {
+              best = score;
+              c.bz = bz; c.by = by; c.bx = bx;
+            }
           }
         }
       }
+      if (best >= 64 * 4) {   // at least a quarter of the 256-row tile in use
+        c.kernel = GK_BRICKR;
+        const int nb = N * (g.D / c.bz) * (g.H / c.by) * (g.W / c.bx);
+        // 32-column tiles where 64-column ones leave fewer than 256 blocks: twice the blocks instead of a chunk split
+        // (no fp32 partials, no reduce launch); 12^3 / 6^3 grouped: 2-8 us per launch (r04v convbench), -0.02 ms/step
+        c.bn = (bf16 && g.Ncols % 64 == 0 && nb * (g.Ncols / 64) >= 256) ? 64 : 32;
+        const int nt = (g.Ncols + c.bn - 1) / c.bn;
+        const int slots = knob("MMSEG_BRICKR_SLOTS", 256);   // 512 measured 2-10 % slower at 12^3 / 6^3 (r02)
+        const auto whole = [](int nchunk, int ks) {   // ks splits as equal ranges of whole chunks
+          ks = std::max(1, std::min(ks, nchunk));
+          const int cps = (nchunk + ks - 1) / ks;
+          return (nchunk + cps - 1) / cps;
+        };
+        c.ks_want = whole(cin / CK, (slots + nb * nt - 1) / (nb * nt));
+        const int nchunk = gemm_nchunk(g);
+        c.ksplit = whole(nchunk, g.ksplit);
+        // KW = 2: two waves per SIMD from an in-block split of the chunks (see the kernel); tap t + 1's fragments
+        // read during tap t's MFMAs (PF: at 12^3 / 6^3 a CU holds one block; 5-10 % per launch, r04ab convbench)
+        c.kw2 = bf16 && c.bn == 32 && c.bz == 6 && c.by == 6 && c.bx == 6 && (nchunk + c.ksplit - 1) / c.ksplit >= 2;
+        c.name = c.bn == 64 ? "conv3_brickr_kernel<BN64>"
+                 : c.kw2    ? "conv3_brickr_kernel<BN32,KW2>" : "conv3_brickr_kernel<BN32>";
+        c.grid = nb * nt * c.ksplit;
+        c.block = c.kw2 ? 512 : 256;
+        c.reduce = c.ksplit > 1;
+        return c;
+      }
     }
-    if (best >= 64 * 4) {   // at least a quarter of the 256-row tile in use
-      p.kind = 2;
-      p.bn = (tsize == 2 && Ncols % 64 == 0) ? 64 : 32;
-      const int nb = (M / (D * H * W)) * (D / p.bz) * (H / p.by) * (W / p.bx);
-      // 32-column tiles where 64-column ones leave fewer than 256 blocks: twice the blocks instead of a chunk split
-      // (no fp32 partials, no reduce launch); 12^3 / 6^3 grouped: 2-8 us per launch (r04v convbench), -0.02 ms/step
-      if (p.bn == 64 && nb * (Ncols / 64) < 256) p.bn = 32;
-      const int nt = (Ncols + p.bn - 1) / p.bn;
-      const int nchunk = cin / CK;
-      const int slots = knob("MMSEG_BRICKR_SLOTS", 256);   // 512 measured 2-10 % slower at 12^3 / 6^3 (r02)
-      int ks = (slots + nb * nt - 1) / (nb * nt);
-      if (ks > nchunk) ks = nchunk;
-      if (ks < 1) ks = 1;
-      const int cps = (nchunk + ks - 1) / ks;
-      p.ks = (nchunk + cps - 1) / cps;
-      return p;
+    if (fam && g.ksplit == 1) {
+      const int nchunk = gemm_nchunk(g);
+      // launches only brick6 serves pass by brick8 and the 96-column rule on their way to it
+      const bool only6 = g.nmean || g.inpart || g.wdq;
+      // 8-wave 8x8x8 brick with LDS-DMA staging (conv3_brick8_kernel), bf16, 16-B output stores
+      // (BN64: one 64-column tile over >= 2 input chunks, where it measured faster than brick2 BN64 -- 48^3
+      // 64->64 fwd / dgrad 61 -> 55.5 us, 128->64 fwd 111 -> 98 us; with one chunk, or two column tiles, it was
+      // slower: profiles/r03c_brick8_convbench.txt)
+      const int b8 = knob("MMSEG_BRICK8", 1), nb8 = nb1 / 2;   // 8-deep bricks
+      const bool b8_ok = bf16 && b8 && !only6 && g.H % 8 == 0 && g.W % 8 == 0 && out16 &&
+                         (!g.out2 || g.ldo2 % 8 == 0) && a31 &&
+                         (long long)((g.KG + 3) & ~3) * g.Cpad * 16 < (1LL << 31);
+      c.kernel = GK_BRICK8;
+      c.block = 512;
+      if (b8_ok && g.Ncols % 64 == 0 && (b8 == 2 || (g.Ncols == 64 && nchunk >= 2)) && g.D % 8 == 0 &&
+          nb8 * (g.Ncols / 64) >= knob("MMSEG_BRICK8_MINBLK", 256)) {
+        c.name = "conv3_brick8_kernel<BN64>";
+        c.bn = 64;
+        c.grid = nb8 * (g.Ncols / 64);
+        return c;
+      }
+      if (b8_ok && g.Ncols == 32 && g.D % 16 == 0 && nb8 / 2 >= knob("MMSEG_BRICK8_MINBLK", 256) && cin >= 64) {
+        c.name = "conv3_brick8_kernel<BN32>";
+        c.bn = 32;
+        c.grid = nb8 / 2;
+        return c;
+      }
+      c.block = 256;
+      // v3 is bf16 only: its fp32 instantiation (f32 16x16x4 MFMA with swapped operands) returned the first
+      // row of each 4-row accumulator group in all four registers (tools/diag_b3.py); the fp32 parity path
+      // keeps the v2 kernel.
+      const bool v3 = bf16 && a31;
+      const bool wide = g.Ncols % 64 == 0 && nb1 * (g.Ncols / 64) >= knob("MMSEG_BRICK2_MINBLK", 512);
+      // 48-column tiles also for multiples of 96 that are not of 64 (SwinUNETR's 96-column convs: two 48-column tiles
+      // read the A halo twice, three 32-column brick3 tiles three times -- 128^3 96-column dgrad 0.74 ms at 706 TF/s
+      // on brick3, r05c timer)
+      if (g.Ncols % 32 != 0 || (!only6 && g.Ncols % 96 == 0 && g.Ncols % 64 != 0)) {   // a multiple of 48
+        c.kernel = GK_BRICK2_BN48;
+        c.name = "conv3_brick2_kernel<BN48,ZW1>";
+        c.bn = 48;
+        c.grid = nb1 * (g.Ncols / 48);
+      } else if (v3 && nchunk == 1 && !wide) {
+        // one persistent block per CU, each over a contiguous brick range of one 32-column tile; brick6 where its
+        // 4x4x16 bricks divide the volume and the output takes 16-B stores
+        const bool b6 = g.H % 4 == 0 && g.W % 16 == 0 && out16;
+        const int nt_n = g.Ncols / 32;
+        const int per_nt = std::max(1, knob("MMSEG_BRICK4_BLOCKS", 256) / nt_n);
+        const int nb = b6 ? N * (g.D / 4) * (g.H / 4) * (g.W / 16) : nb1;
+        c.kernel = b6 ? GK_BRICK6 : GK_BRICK4;
+        c.name = !b6 ? "conv3_brick4_kernel<BN32>" : g.wdq ? "conv3_brick6_kernel<BN32,F8>"
+                 : g.inpart ? "conv3_brick6_kernel<BN32,INP>" : "conv3_brick6_kernel<BN32>";
+        c.bn = 32;
+        c.upb = ceil_div(nb, std::min(per_nt, nb));
+        c.bpn = ceil_div(nb, c.upb);
+        c.grid = c.bpn * nt_n;
+      } else if (v3 && !wide) {
+        // persistent: at most one wave of resident blocks (2 per CU), each over a contiguous range of units
+        const int units = nb1 * (g.Ncols / 32), maxblk = knob("MMSEG_BRICK3_BLOCKS", 512);
+        c.kernel = GK_BRICK3;
+        c.name = "conv3_brick3_kernel<BN32>";
+        c.bn = 32;
+        c.upb = maxblk > 0 ? ceil_div(units, maxblk) : 1;
+        c.grid = ceil_div(units, c.upb);
+      } else {
+        // wide: each tap's fragments read while the previous tap's MFMAs run (2 % on the 48^3 64-channel layers, r02)
+        c.kernel = GK_BRICK2;
+        c.name = wide ? "conv3_brick2_kernel<BN64,ZW1>" : "conv3_brick2_kernel<BN32,ZW1>";
+        c.bn = wide ? 64 : 32;
+        c.grid = nb1 * (g.Ncols / c.bn);
+      }
+      return c;
+    }
+    // per-lane gather GEMM: enough (128 x 64|32) tiles to fill the chip
+    const int tiles = ceil_div(g.M, 128) * ceil_div(g.Ncols, g.Ncols >= 64 ? 64 : 32);
+    if (!fam && tiles < 512 && g.KG >= 32) c.ks_want = std::max(1, std::min(ceil_div(512, tiles), g.KG / 16));
+    if (g.ksplit == 1 && brick == 1 && cin % CK == 0 && g.D % BRK_Z == 0 && g.H % BRK_Y == 0 && g.W % BRK_X == 0 &&
+        g.lda % 8 == 0) {
+      c.kernel = GK_BRICK1;
+      c.bn = g.Ncols >= 64 ? 64 : 32;
+      c.name = c.bn == 64 ? "conv3_brick_kernel<BN64>" : "conv3_brick_kernel<BN32>";
+      c.grid = N * (g.D / BRK_Z) * (g.H / BRK_Y) * (g.W / BRK_X) * ceil_div(g.Ncols, c.bn);
+      return c;
     }
   }
-  if (k1_ok) p.kind = 1;
-  return p;
+  // the gather GEMM's tiles (BM x BN)
+  static const char* const nm32[4] = {"conv_gemm_kernel<conv3,128x32>", "conv_gemm_kernel<point,128x32>",
+                                      "conv_gemm_kernel<convT_fwd,128x32>", "conv_gemm_kernel<convT_dgrad,128x32>"};
+  static const char* const nm64[4] = {"conv_gemm_kernel<conv3,128x64>", "conv_gemm_kernel<point,128x64>",
+                                      "conv_gemm_kernel<convT_fwd,128x64>", "conv_gemm_kernel<convT_dgrad,128x64>"};
+  const bool point1 = mode == MODE_POINT && g.ksplit == 1;
+  const auto pick = [&](int kernel, const char* name, int bn) { c.kernel = kernel; c.name = name; c.bn = bn; };
+  int bm = 128;
+  if (mode == MODE_CONVT_FWD && g.Ncols % 256 == 0) {
+    // a block writes all 8 taps x 32 (or a quarter of 8 x 128 ...) output channels of its 64 input voxels, so
+    // each input row is read by one block instead of by Ncols / 64 column tiles
+    pick(GK_GEMM_64x256, "conv_gemm_kernel<convT_fwd,64x256>", 256);
+    bm = 64;
+  } else if (point1 && g.Ncols > 128 && g.Ncols <= 192 && g.Cpad >= 192) {
+    // SwinUNETR's 144 / 192-column token linears (qkv, MLP fc1, fc2's data gradient) with every A row read by one
+    // block -- 128x64 tiles re-read each K-wide row from L2 / HBM once per column tile
+    pick(GK_GEMM_64x192, "conv_gemm_kernel<point,64x192>", 192);
+    bm = 64;
+  } else if (point1 && g.Ncols > 64 && g.Ncols <= 128 && g.Ncols % 96 != 0) {
+    // 128-column outputs (the residual 1x1 convs' data gradients written as whole 96-of-128 rows) in one column
+    // tile -- the 128x64 tile read every A row twice (the 128^3 decoder's: 295 us, r06k)
+    pick(GK_GEMM_64x128, "conv_gemm_kernel<point,64x128>", 128);
+    bm = 64;
+  } else if (point1 && g.Ncols > 32 && g.Ncols <= 48 && g.Ncols % 16 == 0) {
+    // the 48-column token linears / 1x1 convs (feature_size 48) in one column tile (BN=32 took two)
+    pick(GK_GEMM_128x48, "conv_gemm_kernel<point,128x48>", 48);
+  } else if (mode == MODE_POINT && g.Ncols % 96 == 0 && g.Ncols % 64 != 0) {
+    // the 96 / 288 / 480-column 1x1 GEMMs (SwinUNETR's 96-channel stage, the 96 -> 48 residual conv's data
+    // gradient) in whole tiles -- BN=64 left a half-empty last column tile that re-read every A row
+    pick(GK_GEMM_128x96, "conv_gemm_kernel<point,128x96>", 96);
+  } else if (g.Ncols < 64) {
+    pick(GK_GEMM_128x32, nm32[mode], 32);
+  } else {
+    pick(GK_GEMM_128x64, nm64[mode], 64);
+  }
+  c.grid = ceil_div(g.M, bm) * ceil_div(g.Ncols, c.bn) * g.ksplit;
+  c.reduce = g.ksplit > 1;
+  return c;
 }
 
-// True when launch_gemm<bf16, CONV3> runs conv3_brick6_kernel for this shape (the only conv kernel that
-// applies a deferred InstanceNorm + ReLU to its A source): the conditions of its branch in launch_gemm and of
-// every branch taken before it.
-bool brick6_selected(const GemmArgs& g, int tsize) {
-  if (tsize != 2 || g.ksplit != 1) return false;
-  const Conv3Plan plan = plan_conv3(g.M, g.Ncols, 8 << g.cpg_shift, g.D, g.H, g.W, g.lda, g.ldo, tsize);
-  if (plan.kind != 1) return false;
-  const int nb1 = (g.M / (g.D * g.H * g.W)) * (g.D / 4) * (g.H / B2_Y) * (g.W / B2_X);
-  const int min_blocks = knob("MMSEG_BRICK2_MINBLK", 512);
-  const bool v3 = (long long)g.M * g.lda * 2LL < (1LL << 31);
-  const bool wide = g.Ncols % 64 == 0 && nb1 * (g.Ncols / 64) >= min_blocks;
-  if (!v3 || g.Ncols % 32 != 0 || gemm_nchunk(g) != 1 || wide) return false;
-  return g.H % 4 == 0 && g.W % 16 == 0 && g.ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0;
+// The shape fields of a launch's GemmArgs -- all choose_gemm reads besides the output pointers (null: 16-B aligned,
+// unsplit) and the brick6-only inputs -- with the K range cut into ksplit ranges of whole groups of 4 k-groups.
+GemmArgs gemm_shape(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
+                    int ksplit = 1, int cin_real = 0) {
+  GemmArgs g{};
+  g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
+  g.D = D; g.H = H; g.W = W;
+  const int KGp = (KG + 3) & ~3;
+  g.kg_per_split = ((ceil_div(KGp, ksplit) + 3) / 4) * 4;
+  g.ksplit = ceil_div(KGp, g.kg_per_split);
+  g.swz = 1;   // XCD-aware block remap
+  g.kchunks = (cin_real + 31) / 32;
+  return g;
+}
+// The planning queries: the choice of a 3^3 conv from its shape alone.  flags: what the launch would carry, the bits
+// of mmseg_conv3_kernel / mmseg_conv3_wgrad_kernel.
+enum ChoiceFlags { CF_NORM = 1, CF_INPART = 2, CF_FP8 = 4, CF_GROUPS = 8, CF_PAD16 = 16 };
+GemmChoice choose_conv3(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
+                        int dtype, int flags = 0, int ksplit = 1, int cin_real = 0) {
+  static float set = 0.f;   // any non-null address: choose_gemm only asks whether the launch carries these
+  GemmArgs g = gemm_shape(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, ksplit < 1 ? 1 : ksplit, cin_real);
+  if (flags & CF_NORM) g.nmean = &set;
+  if (flags & CF_INPART) g.inpart = &set;
+  if (flags & CF_FP8) g.wdq = &set;
+  g.grp_n = (flags & CF_GROUPS) ? 1 : 0;
+  return choose_gemm(g, MODE_CONV3, dtype == MMSEG_BF16 ? 2 : 4);
 }
 
 // Every column tile of a conv launch reads weight columns [n0, n0 + BN) of the packed image [KGp][Cpad][8]: all of
@@ -2133,31 +2297,19 @@ inline bool tile_in_pitch(const GemmArgs& g, int BN) { return (long long)((g.Nco
   } while (0)
 
 // The W % 16 one-chunk 32-column conv: brick6 (forward, deferred-norm forward, e4m3 forward, and the data gradient
-// with the InstanceNorm-backward partials).  Returns the bricks per block.
-int launch_brick6(const GemmArgs& g, hipStream_t s) {
-  const int nt_n = g.Ncols / 32;
-  const int per_nt = std::max(1, knob("MMSEG_BRICK4_BLOCKS", 256) / nt_n);
-  const int nb6 = (g.M / (g.D * g.H * g.W)) * (g.D / 4) * (g.H / 4) * (g.W / 16);
-  const int upb6 = ceil_div(nb6, std::min(per_nt, nb6));
-  const int bpn6 = ceil_div(nb6, upb6);
-  const dim3 grid(bpn6 * nt_n), block(256);
+// with the InstanceNorm-backward partials), on the grid choose_gemm gave it.
+void launch_brick6(const GemmArgs& g, const GemmChoice& c, hipStream_t s) {
+  const dim3 grid(c.grid), block(c.block);
   if (g.wdq) {   // e4m3 forward (mmseg_conv3_fwd_fp8)
-    MMSEG_TILE(g, "conv3_brick6_kernel<BN32,F8>", 32);
-    if (g.nmean) MMSEG_LAUNCH((conv3_brick6_kernel<true, 6, false, true>), grid, block, 0, s, g, upb6, bpn6);
-    else MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, false, true>), grid, block, 0, s, g, upb6, bpn6);
-    return upb6;
+    if (g.nmean) MMSEG_LAUNCH((conv3_brick6_kernel<true, 6, false, true>), grid, block, 0, s, g, c.upb, c.bpn);
+    else MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, false, true>), grid, block, 0, s, g, c.upb, c.bpn);
+  } else if (g.inpart) {   // mmseg_conv3_dgrad_in (no bias); the kernel zeroes the partials of samples a block does not touch
+    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, true>), grid, block, 0, s, g, c.upb, c.bpn);
+  } else if (g.nmean) {
+    MMSEG_LAUNCH((conv3_brick6_kernel<true, 6>), grid, block, 0, s, g, c.upb, c.bpn);
+  } else {
+    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6>), grid, block, 0, s, g, c.upb, c.bpn);
   }
-  if (g.inpart) {   // mmseg_conv3_dgrad_in (no bias); the kernel zeroes the partials of samples a block does not touch
-    MMSEG_TILE(g, "conv3_brick6_kernel<BN32,INP>", 32);
-    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, true>), grid, block, 0, s, g, upb6, bpn6);
-    return upb6;
-  }
-  MMSEG_TILE(g, "conv3_brick6_kernel<BN32>", 32);
-  if (g.nmean)
-    MMSEG_LAUNCH((conv3_brick6_kernel<true, 6>), grid, block, 0, s, g, upb6, bpn6);
-  else
-    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6>), grid, block, 0, s, g, upb6, bpn6);
-  return upb6;
 }
 
 // 4 consecutive columns per thread in gemm_splitk_reduce (for the transposed conv: 4 channels of one child voxel,
@@ -2319,7 +2471,7 @@ struct WgradArgs {
   // activation, staged as relu((x - nmean[n][c]) * nrstd[n][c]) rounded to T
   const float* nmean;
   const float* nrstd;
-  int frag;  // wgrad_dma: split partials in the fragment-native layout (wgrad_dma_mt, WReduceArgs::frag_mt)
+  int frag;  // wgrad_dma: split partials in the fragment-native layout (Conv3WgradChoice::fmt, WReduceArgs::frag_mt)
   int groups;  // grouped launch (wgrad_brickr only): the bricks are `groups` equal sample groups, splits
                // [gi * ksplit / groups, (gi + 1) * ksplit / groups) cover group gi's bricks only
   // grouped with one split per group (ksplit == groups) and grad != null: split gi writes group gi's gradient
@@ -4826,241 +4978,117 @@ int launch_splitk_reduce(const GemmArgs& g, hipStream_t s) {
   return mmseg::check_launch("gemm_splitk_reduce");
 }
 
+// Launch what choose_gemm chose (and the split-K reduce after it).
 template <typename T, int MODE>
 int launch_gemm(GemmArgs g, hipStream_t s) {
-  if (g.nmean) {   // deferred InstanceNorm + ReLU of A: brick6 only (mmseg_conv3_norm_ok)
-    MMSEG_REQUIRE(MODE == MODE_CONV3 && brick6_selected(g, (int)sizeof(T)),
-                  "conv3 with a deferred norm needs the brick6 kernel for this shape (mmseg_conv3_norm_ok)");
-    launch_brick6(g, s);
-    return mmseg::check_launch("conv3_brick6_norm");
-  }
-  const int Cbig = g.Ncols >= 64;
-  dim3 block(256);
-  const int brick = knob("MMSEG_BRICK", 2);
-  const Conv3Plan plan = MODE == MODE_CONV3 ? plan_conv3(g.M, g.Ncols, 8 << g.cpg_shift, g.D, g.H, g.W, g.lda, g.ldo,
-                                                         (int)sizeof(T), g.grp_n > 0)
-                                            : Conv3Plan{0, 0, 0, 0, 1, 32};
-  MMSEG_REQUIRE(g.grp_n == 0 || (MODE == MODE_CONV3 && plan.kind == 2),
+  const GemmChoice c = choose_gemm(g, MODE, (int)sizeof(T));
+  MMSEG_REQUIRE(!(g.nmean || g.inpart || g.wdq) || c.kernel == GK_BRICK6,
+                "conv3 with a deferred norm, IN-backward partials or e4m3 weights needs the brick6 kernel for this "
+                "shape (mmseg_conv3_norm_ok / _dgrad_in_chunks / _fp8_ok), not %s", c.name);
+  MMSEG_REQUIRE(g.grp_n == 0 || c.kernel == GK_BRICKR,
                 "grouped conv: only the runtime-brick kernel takes per-group weights (small volumes)");
-  if (plan.kind == 2) {
-    const int nb = (g.M / (g.D * g.H * g.W)) * (g.D / plan.bz) * (g.H / plan.by) * (g.W / plan.bx);
-    const int nchunk = gemm_nchunk(g);
-    if (g.ksplit > nchunk) g.ksplit = nchunk;
-    const int cps = (nchunk + g.ksplit - 1) / g.ksplit;
-    g.ksplit = (nchunk + cps - 1) / cps;
-    const dim3 grid(nb * ((g.Ncols + plan.bn - 1) / plan.bn) * g.ksplit);
-    // compile-time bricks: 6 x 6 x 6 (the 12^3 / 6^3 levels) and 4 x 8 x 8 (the grouped 48^3 / 24^3 levels)
-    const bool b666 = plan.bz == 6 && plan.by == 6 && plan.bx == 6;
-    const bool b488 = plan.bz == 4 && plan.by == 8 && plan.bx == 8;
-    // 32-bit offset halo staging (bf16 only, as conv3_brick2_kernel's B32; MMSEG_B32=0: the 64-bit staging)
-    const bool rb32 = sizeof(T) == 2 && knob("MMSEG_B32", 1) && (long long)g.M * g.lda * (long long)sizeof(T) < (1LL << 31);
-    if (plan.bn == 64) {
-      if constexpr (sizeof(T) == 2) {
-        MMSEG_TILE(g, "conv3_brickr_kernel<BN64>", 64);
-        if (b666 && rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6, false, true>), grid, block, 0, s, g, 6, 6, 6);
-        else if (b666)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6);
-        else if (b488 && rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8, false, true>), grid, block, 0, s, g, 4, 8, 8);
-        else if (b488)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8);
-        else if (rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 0, 0, 0, false, true>), grid, block, 0, s, g, plan.bz, plan.by,
-                       plan.bx);
-        else
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 64>), grid, block, 0, s, g, plan.bz, plan.by, plan.bx);
-      }
-    } else if (b666) {
-      // KW = 2: two waves per SIMD from an in-block split of the chunks (see the kernel); tap t + 1's fragments
-      // read during tap t's MFMAs (PF: at 12^3 / 6^3 a CU holds one block; 5-10 % per launch, r04ab convbench)
-      const bool kw2 = sizeof(T) == 2 && cps >= 2;
-      MMSEG_TILE(g, kw2 ? "conv3_brickr_kernel<BN32,KW2>" : "conv3_brickr_kernel<BN32>", 32);
-      bool done = false;
-      if constexpr (sizeof(T) == 2) {   // (the fp32 form's two stage sets exceed the LDS)
-        const dim3 b2(512);
-        if (kw2 && rb32)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, true, 2>), grid, b2, 0, s, g, 6, 6, 6);
-        else if (kw2)
-          MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, false, 2>), grid, b2, 0, s, g, 6, 6, 6);
-        done = kw2;
-      }
-      if (done) {
-      } else if (rb32)
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, true>), grid, block, 0, s, g, 6, 6, 6);
-      else
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6);
-    } else if (b488) {
-      MMSEG_TILE(g, "conv3_brickr_kernel<BN32>", 32);
-      if (rb32)
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8, false, true>), grid, block, 0, s, g, 4, 8, 8);
-      else
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8);
-    } else {
-      MMSEG_TILE(g, "conv3_brickr_kernel<BN32>", 32);
-      if (rb32)
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 0, 0, 0, false, true>), grid, block, 0, s, g, plan.bz, plan.by,
-                     plan.bx);
-      else
-        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32>), grid, block, 0, s, g, plan.bz, plan.by, plan.bx);
-    }
-    if (mmseg::check_launch("conv3_brickr")) return 1;
-    if (g.ksplit > 1) return launch_splitk_reduce<T, MODE>(g, s);
-    return 0;
-  }
-  if (plan.kind == 1 && g.ksplit == 1) {
-    const int nb1 = (g.M / (g.D * g.H * g.W)) * (g.D / 4) * (g.H / B2_Y) * (g.W / B2_X);
-    const int min_blocks = knob("MMSEG_BRICK2_MINBLK", 512);
-    if constexpr (sizeof(T) == 2) {
-      // 8-wave 8x8x8 brick with LDS-DMA staging (conv3_brick8_kernel)
-      const int nb8 = nb1 / 2;   // 8-deep bricks
-      // (BN64: one 64-column tile over >= 2 input chunks, where it measured faster than brick2 BN64 -- 48^3
-      // 64->64 fwd / dgrad 61 -> 55.5 us, 128->64 fwd 111 -> 98 us; with one chunk, or two column tiles, it was
-      // slower: profiles/r03c_brick8_convbench.txt)
-      const int b8 = knob("MMSEG_BRICK8", 1);
-      if (b8 && g.Ncols % 64 == 0 && (b8 == 2 || (g.Ncols == 64 && gemm_nchunk(g) >= 2)) && g.D % 8 == 0 &&
-          g.H % 8 == 0 && g.W % 8 == 0 &&
-          g.nmean == nullptr && g.inpart == nullptr && g.ldo % 8 == 0 &&
-          (!g.out2 || g.ldo2 % 8 == 0) && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0 &&
-          nb8 * (g.Ncols / 64) >= knob("MMSEG_BRICK8_MINBLK", 256) &&
-          (long long)g.M * g.lda * 2 < (1LL << 31) && (long long)((g.KG + 3) & ~3) * g.Cpad * 16 < (1LL << 31)) {
-        MMSEG_TILE(g, "conv3_brick8_kernel<BN64>", 64);
-        MMSEG_LAUNCH((conv3_brick8_kernel<64, 1>), dim3(nb8 * (g.Ncols / 64)), dim3(512), 0, s, g);
-        return mmseg::check_launch("conv3_brick8");
-      }
-      if (b8 && g.Ncols == 32 && g.D % 16 == 0 && g.H % 8 == 0 && g.W % 8 == 0 &&
-          g.nmean == nullptr && g.inpart == nullptr && g.ldo % 8 == 0 &&
-          (!g.out2 || g.ldo2 % 8 == 0) && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0 &&
-          nb8 / 2 >= knob("MMSEG_BRICK8_MINBLK", 256) && (8 << g.cpg_shift) >= 64 &&
-          (long long)g.M * g.lda * 2 < (1LL << 31) && (long long)((g.KG + 3) & ~3) * g.Cpad * 16 < (1LL << 31)) {
-        MMSEG_TILE(g, "conv3_brick8_kernel<BN32>", 32);
-        MMSEG_LAUNCH((conv3_brick8_kernel<32, 2>), dim3(nb8 / 2), dim3(512), 0, s, g);
-        return mmseg::check_launch("conv3_brick8");
-      }
-    }
-    // v3 is bf16 only: its fp32 instantiation (f32 16x16x4 MFMA with swapped operands) returned the first
-    // row of each 4-row accumulator group in all four registers (tools/diag_b3.py); the fp32 parity path
-    // keeps the v2 kernel.
-    const bool v3 = sizeof(T) == 2 && (long long)g.M * g.lda * (long long)sizeof(T) < (1LL << 31);
-    // persistent: at most one wave of resident blocks (2 per CU), each over a contiguous range of units
-    const int maxblk = knob("MMSEG_BRICK3_BLOCKS", 512);
-    // 32-bit offset halo staging (brick2 B32; bf16 only, see the runtime-brick branch)
-    const bool b32 = sizeof(T) == 2 && knob("MMSEG_B32", 1) && (long long)g.M * g.lda * (long long)sizeof(T) < (1LL << 31);
-    const bool wide = g.Ncols % 64 == 0 && nb1 * (g.Ncols / 64) >= min_blocks;
-    // 48-column tiles also for multiples of 96 that are not of 64 (SwinUNETR's 96-column convs: two 48-column tiles
-    // read the A halo twice, three 32-column brick3 tiles three times -- 128^3 96-column dgrad 0.74 ms at 706 TF/s
-    // on brick3, r05c timer)
-    const bool bn48 = g.Ncols % 32 != 0 || (g.Ncols % 96 == 0 && g.Ncols % 64 != 0);
-    if (bn48) {    // a multiple of 48 (plan_conv3)
-      MMSEG_TILE(g, "conv3_brick2_kernel<BN48,ZW1>", 48);
-      if (b32) {
-        MMSEG_LAUNCH((conv3_brick2_kernel<T, 48, 1, false, true>), dim3(nb1 * (g.Ncols / 48)), block, 0, s, g);
-        return mmseg::check_launch("conv3_brick2");
-      }
-      MMSEG_LAUNCH((conv3_brick2_kernel<T, 48, 1>), dim3(nb1 * (g.Ncols / 48)), block, 0, s, g);
-    } else if (v3 && gemm_nchunk(g) == 1 && g.Ncols % 32 == 0 && !wide) {
-      if constexpr (sizeof(T) == 2) {
-        // one persistent block per CU, each over a contiguous brick range of one 32-column tile
-        const int nt_n = g.Ncols / 32;
-        const int per_nt = std::max(1, knob("MMSEG_BRICK4_BLOCKS", 256) / nt_n);
-        const int upb = ceil_div(nb1, std::min(per_nt, nb1));
-        const int bpn = ceil_div(nb1, upb);
-        if (g.H % 4 == 0 && g.W % 16 == 0 && g.ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0) {
-          launch_brick6(g, s);   // (16-B output stores)
-        } else {
-          MMSEG_TILE(g, "conv3_brick4_kernel<BN32>", 32);
-          MMSEG_LAUNCH(conv3_brick4_kernel, dim3(bpn * nt_n), block, 0, s, g, upb, bpn);
+  MMSEG_TILE(g, c.name, c.bn);
+  g.ksplit = c.ksplit;
+  const dim3 grid(c.grid), block(c.block);
+  // compile-time bricks: 6 x 6 x 6 (the 12^3 / 6^3 levels) and 4 x 8 x 8 (the grouped 48^3 / 24^3 levels)
+  const bool b666 = c.bz == 6 && c.by == 6 && c.bx == 6;
+  const bool b488 = c.bz == 4 && c.by == 8 && c.bx == 8;
+  const bool rb32 = c.b32;
+  switch (c.kernel) {
+    case GK_BRICKR:
+      if (c.bn == 64) {
+        if constexpr (sizeof(T) == 2) {
+          if (b666 && rb32)
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6, false, true>), grid, block, 0, s, g, 6, 6, 6);
+          else if (b666)
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6);
+          else if (b488 && rb32)
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8, false, true>), grid, block, 0, s, g, 4, 8, 8);
+          else if (b488)
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8);
+          else if (rb32)
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 64, 0, 0, 0, false, true>), grid, block, 0, s, g, c.bz, c.by, c.bx);
+          else
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 64>), grid, block, 0, s, g, c.bz, c.by, c.bx);
         }
+      } else if (c.kw2) {
+        if constexpr (sizeof(T) == 2) {   // (the fp32 form's two stage sets exceed the LDS)
+          const dim3 b2(c.block);
+          if (rb32)
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, true, 2>), grid, b2, 0, s, g, 6, 6, 6);
+          else
+            MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, false, 2>), grid, b2, 0, s, g, 6, 6, 6);
+        }
+      } else if (b666 && rb32) {
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6, true, true>), grid, block, 0, s, g, 6, 6, 6);
+      } else if (b666) {
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 6, 6, 6>), grid, block, 0, s, g, 6, 6, 6);
+      } else if (b488 && rb32) {
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8, false, true>), grid, block, 0, s, g, 4, 8, 8);
+      } else if (b488) {
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 4, 8, 8>), grid, block, 0, s, g, 4, 8, 8);
+      } else if (rb32) {
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32, 0, 0, 0, false, true>), grid, block, 0, s, g, c.bz, c.by, c.bx);
+      } else {
+        MMSEG_LAUNCH((conv3_brickr_kernel<T, 32>), grid, block, 0, s, g, c.bz, c.by, c.bx);
       }
-    } else if (v3 && !wide) {
-      const int units = nb1 * (g.Ncols / 32);
-      const int upb = maxblk > 0 ? ceil_div(units, maxblk) : 1;
-      MMSEG_TILE(g, "conv3_brick3_kernel<BN32>", 32);
-      MMSEG_LAUNCH((conv3_brick3_kernel<T, 32>), dim3(ceil_div(units, upb)), block, 0, s, g, upb);
-    } else if (wide) {
-      // each tap's fragments read while the previous tap's MFMAs run (2 % on the 48^3 64-channel layers, r02)
-      MMSEG_TILE(g, "conv3_brick2_kernel<BN64,ZW1>", 64);
-      if (b32)
-        MMSEG_LAUNCH((conv3_brick2_kernel<T, 64, 1, true, true>), dim3(nb1 * (g.Ncols / 64)), block, 0, s, g);
+      if (mmseg::check_launch(c.name)) return 1;
+      return c.reduce ? launch_splitk_reduce<T, MODE>(g, s) : 0;
+    case GK_BRICK8:
+      if constexpr (sizeof(T) == 2) {
+        if (c.bn == 64) MMSEG_LAUNCH((conv3_brick8_kernel<64, 1>), grid, block, 0, s, g);
+        else MMSEG_LAUNCH((conv3_brick8_kernel<32, 2>), grid, block, 0, s, g);
+      }
+      break;
+    case GK_BRICK2_BN48:
+      if (c.b32) MMSEG_LAUNCH((conv3_brick2_kernel<T, 48, 1, false, true>), grid, block, 0, s, g);
+      else MMSEG_LAUNCH((conv3_brick2_kernel<T, 48, 1>), grid, block, 0, s, g);
+      break;
+    case GK_BRICK6:
+      launch_brick6(g, c, s);
+      break;
+    case GK_BRICK4:
+      if constexpr (sizeof(T) == 2) MMSEG_LAUNCH(conv3_brick4_kernel, grid, block, 0, s, g, c.upb, c.bpn);
+      break;
+    case GK_BRICK3:
+      MMSEG_LAUNCH((conv3_brick3_kernel<T, 32>), grid, block, 0, s, g, c.upb);
+      break;
+    case GK_BRICK2:
+      if (c.bn == 64 && c.b32)
+        MMSEG_LAUNCH((conv3_brick2_kernel<T, 64, 1, true, true>), grid, block, 0, s, g);
+      else if (c.bn == 64)
+        MMSEG_LAUNCH((conv3_brick2_kernel<T, 64, 1, true>), grid, block, 0, s, g);
       else
-        MMSEG_LAUNCH((conv3_brick2_kernel<T, 64, 1, true>), dim3(nb1 * (g.Ncols / 64)), block, 0, s, g);
-    } else {
-      MMSEG_TILE(g, "conv3_brick2_kernel<BN32,ZW1>", 32);
-      MMSEG_LAUNCH((conv3_brick2_kernel<T, 32, 1>), dim3(nb1 * (g.Ncols / 32)), block, 0, s, g);
-    }
-    return mmseg::check_launch("conv3_brick2");
+        MMSEG_LAUNCH((conv3_brick2_kernel<T, 32, 1>), grid, block, 0, s, g);
+      break;
+    case GK_BRICK1:
+      if (c.bn == 64) MMSEG_LAUNCH((conv3_brick_kernel<T, 64>), grid, block, 0, s, g);
+      else MMSEG_LAUNCH((conv3_brick_kernel<T, 32>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_64x256:
+      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 1, 4, 4, 4>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_64x192:
+      if constexpr (MODE == MODE_POINT) MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 1, 4, 4, 3>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_64x128:
+      if constexpr (MODE == MODE_POINT) MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 1, 4, 4, 2>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_128x48:
+      if constexpr (MODE == MODE_POINT) MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 4, 1, 2, 3>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_128x96:
+      if constexpr (MODE == MODE_POINT) MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 2, 2, 4, 3>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_128x32:
+      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 4, 1, 2, 2>), grid, block, 0, s, g);
+      break;
+    case GK_GEMM_128x64:
+      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 2, 2, 4, 2>), grid, block, 0, s, g);
+      break;
   }
-  if (MODE == MODE_CONV3 && g.ksplit == 1 && brick == 1 && (8 << g.cpg_shift) % CK == 0 &&
-      g.D % BRK_Z == 0 && g.H % BRK_Y == 0 && g.W % BRK_X == 0 && g.lda % 8 == 0) {
-    const int nb = (g.M / (g.D * g.H * g.W)) * (g.D / BRK_Z) * (g.H / BRK_Y) * (g.W / BRK_X);
-    const int bn = g.Ncols >= 64 ? 64 : 32;
-    MMSEG_TILE(g, bn == 64 ? "conv3_brick_kernel<BN64>" : "conv3_brick_kernel<BN32>", bn);
-    if (bn == 64) {
-      MMSEG_LAUNCH((conv3_brick_kernel<T, 64>), dim3(nb * ceil_div(g.Ncols, 64)), block, 0, s, g);
-    } else {
-      MMSEG_LAUNCH((conv3_brick_kernel<T, 32>), dim3(nb * ceil_div(g.Ncols, 32)), block, 0, s, g);
-    }
-    return mmseg::check_launch("conv3_brick");
-  }
-  if (MODE == MODE_CONVT_FWD && g.Ncols % 256 == 0) {
-    // BM=64, BN=256: a block writes all 8 taps x 32 (or a quarter of 8 x 128 ...) output channels of its 64 input
-    // voxels, so each input row is read by one block instead of by Ncols / 64 column tiles
-    MMSEG_TILE(g, "conv_gemm_kernel<convT_fwd,64x256>", 256);
-    dim3 grid(ceil_div(g.M, 64) * (g.Ncols / 256) * g.ksplit);
-    MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 1, 4, 4, 4>), grid, block, 0, s, g);
-    if (mmseg::check_launch("conv_gemm")) return 1;
-    if (g.ksplit > 1) return launch_splitk_reduce<T, MODE>(g, s);
-    return 0;
-  }
-  if (MODE == MODE_POINT && g.ksplit == 1 && g.Ncols > 128 && g.Ncols <= 192 && g.Cpad >= 192) {
-    // BM=64, BN=192: SwinUNETR's 144 / 192-column token linears (qkv, MLP fc1, fc2's data gradient) with every A
-    // row read by one block -- 128x64 tiles re-read each K-wide row from L2 / HBM once per column tile
-    if constexpr (MODE == MODE_POINT) {
-      MMSEG_TILE(g, "conv_gemm_kernel<point,64x192>", 192);
-      dim3 grid(ceil_div(g.M, 64));
-      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 1, 4, 4, 3>), grid, block, 0, s, g);
-    }
-  } else if (MODE == MODE_POINT && g.ksplit == 1 && g.Ncols > 64 && g.Ncols <= 128 && g.Ncols % 96 != 0) {
-    // BM=64, BN=128: 128-column outputs (the residual 1x1 convs' data gradients written as whole 96-of-128 rows)
-    // in one column tile -- the 128x64 tile read every A row twice (the 128^3 decoder's: 295 us, r06k)
-    if constexpr (MODE == MODE_POINT) {
-      MMSEG_TILE(g, "conv_gemm_kernel<point,64x128>", 128);
-      dim3 grid(ceil_div(g.M, 64));
-      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 1, 4, 4, 2>), grid, block, 0, s, g);
-    }
-  } else if (MODE == MODE_POINT && g.ksplit == 1 && g.Ncols > 32 && g.Ncols <= 48 && g.Ncols % 16 == 0) {
-    // BM=128, BN=48: the 48-column token linears / 1x1 convs (feature_size 48) in one column tile (BN=32 took two)
-    if constexpr (MODE == MODE_POINT) {
-      MMSEG_TILE(g, "conv_gemm_kernel<point,128x48>", 48);
-      dim3 grid(ceil_div(g.M, 128));
-      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 4, 1, 2, 3>), grid, block, 0, s, g);
-    }
-  } else if (MODE == MODE_POINT && g.Ncols % 96 == 0 && g.Ncols % 64 != 0) {
-    // BM=128, BN=96: the 96 / 288 / 480-column 1x1 GEMMs (SwinUNETR's 96-channel stage, the 96 -> 48 residual
-    // conv's data gradient) in whole tiles -- BN=64 left a half-empty last column tile that re-read every A row
-    if constexpr (MODE == MODE_POINT) {
-      MMSEG_TILE(g, "conv_gemm_kernel<point,128x96>", 96);
-      dim3 grid(ceil_div(g.M, 128) * (g.Ncols / 96) * g.ksplit);
-      MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 2, 2, 4, 3>), grid, block, 0, s, g);
-    }
-  } else if (!Cbig) {
-    // BM=128, BN=32
-    static const char* nm[4] = {"conv_gemm_kernel<conv3,128x32>", "conv_gemm_kernel<point,128x32>",
-                                "conv_gemm_kernel<convT_fwd,128x32>", "conv_gemm_kernel<convT_dgrad,128x32>"};
-    MMSEG_TILE(g, nm[MODE], 32);
-    dim3 grid(ceil_div(g.M, 128) * ceil_div(g.Ncols, 32) * g.ksplit);
-    MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 4, 1, 2, 2>), grid, block, 0, s, g);
-  } else {
-    // BM=128, BN=64
-    static const char* nm[4] = {"conv_gemm_kernel<conv3,128x64>", "conv_gemm_kernel<point,128x64>",
-                                "conv_gemm_kernel<convT_fwd,128x64>", "conv_gemm_kernel<convT_dgrad,128x64>"};
-    MMSEG_TILE(g, nm[MODE], 64);
-    dim3 grid(ceil_div(g.M, 128) * ceil_div(g.Ncols, 64) * g.ksplit);
-    MMSEG_LAUNCH((conv_gemm_kernel<T, MODE, 2, 2, 4, 2>), grid, block, 0, s, g);
-  }
-  if (mmseg::check_launch("conv_gemm")) return 1;
-  if (g.ksplit > 1) return launch_splitk_reduce<T, MODE>(g, s);
-  return 0;
+  if (mmseg::check_launch(c.name)) return 1;
+  return c.reduce ? launch_splitk_reduce<T, MODE>(g, s) : 0;
 }
 
 template <typename T>
@@ -5081,136 +5109,6 @@ int launch_gemm_mode(GemmArgs g, int mode, hipStream_t s) {
 // of input); 32-co tiles halve them at the price of reading the halo once per row tile.  Below V voxels
 // a threshold the 32-co tiles were tried below (r04: equal or slower at 24^3), so 64-co tiles throughout.
 bool wgrad_co64(int Ca) { return Ca % 64 == 0; }
-
-// The LDS-DMA weight-gradient kernel's row tile (4 = 64 co, 2 = 32 co) when it takes this CONV3 brick2 launch,
-// else 0: bf16, byte offsets of both tensors within 31 bits (the deferred-norm variant keeps register staging by
-// default: its in-place LDS pass and extra barrier cost more than the DMA saves, 0.651 -> 0.682 ms/step for the
-// 32-co family)
-int wgrad_dma_mt(const WgradArgs& g, int elem_bytes) {
-  const bool dma = elem_bytes == 2 && g.brick == 2 && knob("MMSEG_WGRAD_DMA", 1) && g.nmean == nullptr &&
-                   g.V * g.lda * 2 < (1LL << 31) &&
-                   g.V * g.ldb * 2 < (1LL << 31) && (g.lda % 8) == 0 && (g.ldb % 8) == 0;
-  return dma ? (wgrad_co64(g.Ca) ? 4 : 2) : 0;
-}
-
-// the row-slab weight gradient (wgrad_row_kernel) takes the shape: bf16 3^3, 32 output channels, W % 32 == 0,
-// H % 4 == 0, split partials (no direct gradient, no groups, no padded rows), 32-bit DMA offsets
-// rows per step: 6 where H allows (r06c, 96^3 B=2: 32 -> 32 deferred norm 128.6 -> 113.6 us, 64 -> 32 196 -> 179 us
-// against 4 rows; five ring slots or s_setprio for waves 6..11 measured no change), else 4
-bool wgrad_row_ok(const WgradArgs& g, int elem_bytes) {
-  return elem_bytes == 2 && knob("MMSEG_WGRAD_ROW", 1) && g.brick == 2 && g.Ca == 32 && g.W % 32 == 0 &&
-         g.H % 4 == 0 && (8 << g.cpg_shift) % CK == 0 && g.groups == 0 && !g.pad16 && g.ksplit > 1 &&
-         g.V * g.lda * 2 < (1LL << 31) && g.V * g.ldb * 2 < (1LL << 31) && g.lda % 8 == 0 && g.ldb % 8 == 0 &&
-         g.V / ((long long)g.D * g.H * g.W) <= WROW_MAXN;
-}
-
-template <typename T, int MODE>
-int launch_wgrad(WgradArgs g, hipStream_t s) {
-  dim3 block(256);
-  if constexpr (sizeof(T) == 2) {
-    if (MODE == MODE_CONV3 && g.brick == 3) {
-      const WBrick wb = plan_wgrad_brickr(g.D, g.H, g.W);
-      const bool b366 = wb.bz == 3 && wb.by == 6 && wb.bx == 6;
-      const bool b448 = wb.bz == 4 && wb.by == 4 && wb.bx == 8;   // grouped 48^3 / 24^3
-      if (wgrad_co64(g.Ca)) {
-        dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 64) * g.ksplit);
-        // (the compile-time bricks under their rocprofv3 family names, tools/rocprof_families.py)
-        mmseg::note_kernel(b366 ? "wgrad_brickr_kernel<CO64,V3>" : b448 ? "wgrad_brickr_kernel<CO64,B448>"
-                                                                         : "wgrad_brickr_kernel<CO64>");
-        if (b366)
-          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 4, 3, 6, 6>), grid, dim3(512), 0, s, g, 3, 6, 6);
-        else if (b448)
-          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 4, 4, 4, 8>), grid, dim3(512), 0, s, g, 4, 4, 8);
-        else
-          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 4>), grid, dim3(512), 0, s, g, wb.bz, wb.by, wb.bx);
-      } else {
-        dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 32) * g.ksplit);
-        mmseg::note_kernel(b366 ? "wgrad_brickr_kernel<CO32,V3>" : b448 ? "wgrad_brickr_kernel<CO32,B448>"
-                                                                         : "wgrad_brickr_kernel<CO32>");
-        if (b366)
-          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 2, 3, 6, 6>), grid, dim3(512), 0, s, g, 3, 6, 6);
-        else if (b448)
-          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 2, 4, 4, 8>), grid, dim3(512), 0, s, g, 4, 4, 8);
-        else
-          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 2>), grid, dim3(512), 0, s, g, wb.bz, wb.by, wb.bx);
-      }
-      return mmseg::check_launch("wgrad_brickr");
-    }
-    if (MODE == MODE_CONV3 && g.brick == 2 && wgrad_row_ok(g, (int)sizeof(T))) {
-      MMSEG_REQUIRE(g.frag, "wgrad_row: fragment-native partials only");
-      const dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * g.ksplit);
-      auto run = [&](auto normc) {
-        constexpr bool NRM = decltype(normc)::value;
-        if (g.H % 6 == 0)
-          MMSEG_LAUNCH((wgrad_row_kernel<NRM, 6>), grid, dim3(768), 0, s, g);
-        else
-          MMSEG_LAUNCH((wgrad_row_kernel<NRM, 4>), grid, dim3(768), 0, s, g);
-      };
-      if (g.nmean) {
-        mmseg::note_kernel("wgrad_row_kernel<CO32,NORM>");
-        run(std::true_type{});
-      } else {
-        mmseg::note_kernel("wgrad_row_kernel<CO32>");
-        run(std::false_type{});
-      }
-      return mmseg::check_launch("wgrad_row");
-    }
-    if (MODE == MODE_CONV3 && g.brick == 2) {
-      if (const int mt = wgrad_dma_mt(g, (int)sizeof(T))) {
-        dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / (16 * mt)) * g.ksplit);
-        if (mt == 4) {
-          mmseg::note_kernel("wgrad_dma_kernel<CO64>");
-          // 48 real rows of 64 (SwinUNETR's 48-channel levels): three row tiles, room for the pipelined multiply
-          if (g.pad16 && g.Ca == 64)
-            MMSEG_LAUNCH((wgrad_dma_kernel<4, false, 3, true, 3>), grid, dim3(512), 0, s, g);
-          else   // (fragment prefetch two steps ahead spills at 64 co: 59.5 -> 72.3 us)
-            MMSEG_LAUNCH((wgrad_dma_kernel<4>), grid, dim3(512), 0, s, g);
-        } else {
-          mmseg::note_kernel("wgrad_dma_kernel<CO32>");
-          MMSEG_LAUNCH((wgrad_dma_kernel<2, false, 3, true>), grid, dim3(512), 0, s, g);
-        }
-        return mmseg::check_launch("wgrad_dma");
-      }
-      if (wgrad_co64(g.Ca)) {
-        dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 64) * g.ksplit);
-        mmseg::note_kernel("wgrad_brick2_kernel<CO64,V3>");
-        if (g.nmean)
-          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 4, 3, true>), grid, dim3(512), 0, s, g);
-        else
-          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 4, 3>), grid, dim3(512), 0, s, g);
-      } else {
-        // (fragment reads software-pipelined, r05: the deferred-norm 96^3 layers 136 -> 125 us before wgrad_row)
-        dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 32) * g.ksplit);
-        mmseg::note_kernel("wgrad_brick2_kernel<CO32,V3>");
-        if (g.nmean)
-          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 2, 3, true, true>), grid, dim3(512), 0, s, g);
-        else
-          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 2, 3, false, true>), grid, dim3(512), 0, s, g);
-      }
-      return mmseg::check_launch("wgrad_brick2");
-    }
-  }
-  if (MODE == MODE_CONV3 && g.brick) {
-    dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / 32) * g.ksplit);
-    mmseg::note_kernel("wgrad_brick_kernel");
-    MMSEG_LAUNCH((wgrad_brick_kernel<T>), grid, block, 0, s, g);
-    return mmseg::check_launch("wgrad_brick");
-  }
-  static const char* nm[4] = {"wgrad_kernel<conv3>", "wgrad_kernel<point>", "wgrad_kernel<convT_fwd>",
-                              "wgrad_kernel<convT_dgrad>"};
-  mmseg::note_kernel(nm[MODE]);
-  // 1x1 weight gradients take 64-row tiles whatever the row count (rows past Ca are masked): every row tile re-reads
-  // the whole B operand (x), and these launches are HBM-bound -- 48 / 144-row layers read x once / three times
-  // instead of twice / five times with 32-row tiles
-  if (g.Ca % 64 == 0 || MODE == MODE_POINT) {
-    dim3 grid(ceil_div(g.Ncols, 64) * ceil_div(g.Ca, 64) * g.ksplit);
-    MMSEG_LAUNCH((wgrad_kernel<T, MODE, 2, 2, 2, 2, 64>), grid, block, 0, s, g);
-  } else {
-    dim3 grid(ceil_div(g.Ncols, 64) * ceil_div(g.Ca, 32) * g.ksplit);
-    MMSEG_LAUNCH((wgrad_kernel<T, MODE, 1, 4, 2, 1, 64>), grid, block, 0, s, g);
-  }
-  return mmseg::check_launch("wgrad");
-}
 
 // 0: generic wgrad_kernel, 1: wgrad_brick_kernel (32 co), 2: wgrad_brick2_kernel (64 / 32 co),
 // 3: wgrad_brickr_kernel (runtime brick, small volumes).
@@ -5276,22 +5174,36 @@ bool wgrad_direct_ok(int Cip, int Ci) {
   return Ci == Cip || (Ci % 32 == 0 && wgrad_kchunks(Cip, Ci) == Ci / 32);
 }
 
-// CONV3 weight-gradient plan (mmseg_conv3_wgrad): kernel kind (wgrad_brick_ok), split count, whether the
-// kernel writes the torch-layout gradient itself (brick2 / brickr, one split, unpadded input channels),
-// and the workspace (floats) of the split partials + bias partials otherwise.
-struct Conv3WgradPlan {
-  int kind, ksplit, direct;
-  long long ws;
+// ---- the kernel choice of a 3^3 weight gradient (mmseg_conv3_wgrad and its forms).  choose_conv3_wgrad is the only
+// place that decides it: conv3_wgrad_impl launches what it returns, and the planning queries (_ws_floats, _norm_ok,
+// _group_ok, mmseg_conv3_wgrad_kernel) answer from it without a GPU.
+enum WgradKernel { WK_GATHER, WK_BRICK1, WK_BRICK2, WK_DMA, WK_ROW, WK_BRICKR };
+struct Conv3WgradChoice {
+  int kind;          // wgrad_brick_ok
+  int ksplit;
+  int direct;        // the kernel writes the torch-layout gradient itself (brick2 / brickr, one split -- per group --,
+                     // wgrad_direct_ok): no partials, no reduce
+  long long ws;      // floats of split partials + bias partials otherwise
+  int kernel;        // WgradKernel
+  const char* name;  // the family noted for mmseg_last_kernel() / the per-kernel timer
+  int co;            // output-channel rows of a block's tile
+  int fmt;           // split partials: 0 row-major tiles, else fragment-native in fmt 16-row tiles
+                     // (WgradArgs::frag, WReduceArgs::frag_mt)
+  WBrick wb;         // WK_BRICKR: the brick
 };
 
-Conv3WgradPlan plan_conv3_wgrad(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W, int lda,
-                                int ldb, int dtype, long long ws_cap, bool force_r = false) {
-  Conv3WgradPlan p{0, 1, 0, 0};
+// ws_cap: the caller's workspace (floats), which caps the split.  groups > 1 (mmseg_conv3_wgrad_group): the
+// runtime-brick kernel even where the (4, 8, 8)-brick family fits, the split count of the whole V rounded down to a
+// multiple of `groups` (at least one split per group).  norm: x is staged through a deferred InstanceNorm + ReLU.
+Conv3WgradChoice choose_conv3_wgrad(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W, int lda,
+                                    int ldb, int dtype, long long ws_cap, int groups = 1, bool norm = false,
+                                    bool pad16 = false) {
+  Conv3WgradChoice p{};
   const long long ncols = 27LL * Cip;
   const long long per_split = (long long)Co * ncols + Co;
   int cap = (int)(ws_cap / per_split);
   if (cap < 1) cap = 1;
-  p.kind = wgrad_brick_ok(Co, cpg_shift, D, H, W, lda, ldb, dtype, force_r);
+  p.kind = wgrad_brick_ok(Co, cpg_shift, D, H, W, lda, ldb, dtype, groups > 1);
   if (p.kind) {
     p.ksplit = brick_wgrad_splits(V, cap, Co, cpg_shift, p.kind, D, H, W, wgrad_kchunks(Cip, Ci));
   } else {
@@ -5303,9 +5215,139 @@ Conv3WgradPlan plan_conv3_wgrad(long long V, int Co, int Cip, int Ci, int cpg_sh
     if (want < 1) want = 1;
     p.ksplit = mmseg_wgrad_splits_impl(V, (int)want);
   }
-  p.direct = p.kind >= 2 && p.ksplit == 1 && wgrad_direct_ok(Cip, Ci);
+  if (groups > 1) {
+    p.ksplit = std::max(p.ksplit / groups * groups, groups);
+    // one split per group (the deepest levels): each writes its group's gradient directly, as the ungrouped
+    // single-split launch does -- a reduce would only copy 2 x 28 MB there (28.8 us, r04d)
+    p.direct = p.kind >= 2 && p.ksplit == groups && Ci == Cip;
+  } else {
+    p.direct = p.kind >= 2 && p.ksplit == 1 && wgrad_direct_ok(Cip, Ci);
+  }
   p.ws = p.direct ? 0 : p.ksplit * per_split;
+
+  // both tensors within 31 bits of byte offset at 16-B rows (the LDS-DMA kernels; kinds 2 / 3 are bf16)
+  const bool dma_ok = V * lda * 2 < (1LL << 31) && V * ldb * 2 < (1LL << 31) && lda % 8 == 0 && ldb % 8 == 0;
+  p.co = wgrad_co64(Co) ? 64 : 32;
+  if (p.kind == 3) {
+    p.kernel = WK_BRICKR;
+    p.wb = plan_wgrad_brickr(D, H, W);
+    // (the compile-time bricks under their rocprofv3 family names, tools/rocprof_families.py)
+    const bool b366 = p.wb.bz == 3 && p.wb.by == 6 && p.wb.bx == 6;
+    const bool b448 = p.wb.bz == 4 && p.wb.by == 4 && p.wb.bx == 8;   // grouped 48^3 / 24^3
+    p.name = p.co == 64 ? (b366 ? "wgrad_brickr_kernel<CO64,V3>" : b448 ? "wgrad_brickr_kernel<CO64,B448>"
+                                                                         : "wgrad_brickr_kernel<CO64>")
+                        : (b366 ? "wgrad_brickr_kernel<CO32,V3>" : b448 ? "wgrad_brickr_kernel<CO32,B448>"
+                                                                         : "wgrad_brickr_kernel<CO32>");
+  } else if (p.kind == 2 && knob("MMSEG_WGRAD_ROW", 1) && Co == 32 && W % 32 == 0 && H % 4 == 0 && (8 << cpg_shift) % CK == 0 &&
+             groups <= 1 && !pad16 && p.ksplit > 1 && dma_ok && V / ((long long)D * H * W) <= WROW_MAXN) {
+    // the row-slab weight gradient: 32 output channels, W % 32 == 0, H % 4 == 0, split partials (no direct gradient,
+    // no groups, no padded rows), fragment-native partials only (2 co tiles of 16)
+    p.kernel = WK_ROW;
+    p.name = norm ? "wgrad_row_kernel<CO32,NORM>" : "wgrad_row_kernel<CO32>";
+    p.fmt = 2;
+  } else if (p.kind == 2 && knob("MMSEG_WGRAD_DMA", 1) && !norm && dma_ok) {
+    // the LDS-DMA kernel (the deferred-norm variant keeps register staging by default: its in-place LDS pass and
+    // extra barrier cost more than the DMA saves, 0.651 -> 0.682 ms/step for the 32-co family)
+    p.kernel = WK_DMA;
+    p.name = p.co == 64 ? "wgrad_dma_kernel<CO64>" : "wgrad_dma_kernel<CO32>";
+    p.fmt = p.co / 16;
+  } else if (p.kind == 2) {
+    p.kernel = WK_BRICK2;
+    p.name = p.co == 64 ? "wgrad_brick2_kernel<CO64,V3>" : "wgrad_brick2_kernel<CO32,V3>";
+  } else if (p.kind == 1) {
+    p.kernel = WK_BRICK1;
+    p.name = "wgrad_brick_kernel";
+    p.co = 32;
+  } else {
+    p.kernel = WK_GATHER;
+    p.name = "wgrad_kernel<conv3>";
+  }
   return p;
+}
+
+// Launch a weight gradient: what choose_conv3_wgrad chose (CONV3), or the gather kernel (WK_GATHER: the 1x1 and
+// transposed-conv layers, and 3^3 shapes no brick kernel takes).
+template <typename T, int MODE>
+int launch_wgrad(const WgradArgs& g, const Conv3WgradChoice& c, hipStream_t s) {
+  mmseg::note_kernel(c.name);
+  const WBrick wb = c.wb;
+  if (c.kernel != WK_GATHER) {
+    const dim3 grid(wgrad_nchunk(g.cpg_shift, g.kchunks) * (g.Ca / c.co) * g.ksplit);   // (chunk, row tile, split)
+    const bool b366 = wb.bz == 3 && wb.by == 6 && wb.bx == 6, b448 = wb.bz == 4 && wb.by == 4 && wb.bx == 8;
+    if constexpr (sizeof(T) == 2) {   // (v2 / runtime brick are bf16 only: their fp32 stage buffers would not fit in LDS)
+      if (c.kernel == WK_BRICKR && c.co == 64) {
+        if (b366)
+          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 4, 3, 6, 6>), grid, dim3(512), 0, s, g, 3, 6, 6);
+        else if (b448)
+          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 4, 4, 4, 8>), grid, dim3(512), 0, s, g, 4, 4, 8);
+        else
+          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 4>), grid, dim3(512), 0, s, g, wb.bz, wb.by, wb.bx);
+      } else if (c.kernel == WK_BRICKR) {
+        if (b366)
+          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 2, 3, 6, 6>), grid, dim3(512), 0, s, g, 3, 6, 6);
+        else if (b448)
+          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 2, 4, 4, 8>), grid, dim3(512), 0, s, g, 4, 4, 8);
+        else
+          MMSEG_LAUNCH((wgrad_brickr_kernel<T, 2>), grid, dim3(512), 0, s, g, wb.bz, wb.by, wb.bx);
+      } else if (c.kernel == WK_ROW) {
+        // rows per step: 6 where H allows (r06c, 96^3 B=2: 32 -> 32 deferred norm 128.6 -> 113.6 us, 64 -> 32
+        // 196 -> 179 us against 4 rows; five ring slots or s_setprio for waves 6..11 measured no change), else 4
+        auto run = [&](auto normc) {
+          constexpr bool NRM = decltype(normc)::value;
+          if (g.H % 6 == 0)
+            MMSEG_LAUNCH((wgrad_row_kernel<NRM, 6>), grid, dim3(768), 0, s, g);
+          else
+            MMSEG_LAUNCH((wgrad_row_kernel<NRM, 4>), grid, dim3(768), 0, s, g);
+        };
+        if (g.nmean) run(std::true_type{});
+        else run(std::false_type{});
+      } else if (c.kernel == WK_DMA) {
+        // 48 real rows of 64 (SwinUNETR's 48-channel levels): three row tiles, room for the pipelined multiply
+        if (c.co == 64 && g.pad16 && g.Ca == 64)
+          MMSEG_LAUNCH((wgrad_dma_kernel<4, false, 3, true, 3>), grid, dim3(512), 0, s, g);
+        else if (c.co == 64)   // (fragment prefetch two steps ahead spills at 64 co: 59.5 -> 72.3 us)
+          MMSEG_LAUNCH((wgrad_dma_kernel<4>), grid, dim3(512), 0, s, g);
+        else
+          MMSEG_LAUNCH((wgrad_dma_kernel<2, false, 3, true>), grid, dim3(512), 0, s, g);
+      } else if (c.kernel == WK_BRICK2 && c.co == 64) {
+        if (g.nmean)
+          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 4, 3, true>), grid, dim3(512), 0, s, g);
+        else
+          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 4, 3>), grid, dim3(512), 0, s, g);
+      } else if (c.kernel == WK_BRICK2) {
+        // (fragment reads software-pipelined, r05: the deferred-norm 96^3 layers 136 -> 125 us before wgrad_row)
+        if (g.nmean)
+          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 2, 3, true, true>), grid, dim3(512), 0, s, g);
+        else
+          MMSEG_LAUNCH((wgrad_brick2_kernel<T, 2, 3, false, true>), grid, dim3(512), 0, s, g);
+      }
+    }
+    if (c.kernel == WK_BRICK1) MMSEG_LAUNCH((wgrad_brick_kernel<T>), grid, dim3(256), 0, s, g);
+    return mmseg::check_launch(c.name);
+  }
+  // 1x1 weight gradients take 64-row tiles whatever the row count (rows past Ca are masked): every row tile re-reads
+  // the whole B operand (x), and these launches are HBM-bound -- 48 / 144-row layers read x once / three times
+  // instead of twice / five times with 32-row tiles
+  const dim3 block(256);
+  if (g.Ca % 64 == 0 || MODE == MODE_POINT) {
+    dim3 grid(ceil_div(g.Ncols, 64) * ceil_div(g.Ca, 64) * g.ksplit);
+    MMSEG_LAUNCH((wgrad_kernel<T, MODE, 2, 2, 2, 2, 64>), grid, block, 0, s, g);
+  } else {
+    dim3 grid(ceil_div(g.Ncols, 64) * ceil_div(g.Ca, 32) * g.ksplit);
+    MMSEG_LAUNCH((wgrad_kernel<T, MODE, 1, 4, 2, 1, 64>), grid, block, 0, s, g);
+  }
+  return mmseg::check_launch(c.name);
+}
+
+template <typename T>
+int launch_wgrad_mode(const WgradArgs& g, const Conv3WgradChoice& c, int mode, hipStream_t s) {
+  switch (mode) {
+    case MODE_CONV3: return launch_wgrad<T, MODE_CONV3>(g, c, s);
+    case MODE_POINT: return launch_wgrad<T, MODE_POINT>(g, c, s);
+    case MODE_CONVT_DGRAD: return launch_wgrad<T, MODE_CONVT_DGRAD>(g, c, s);
+  }
+  mmseg::set_error("wgrad: bad mode %d", mode);
+  return 1;
 }
 
 // split slices S of a reduce: about 8 split loads per thread, the slice sums a pairwise
@@ -5536,9 +5578,8 @@ int mmseg_conv_gemm_gelu(const void* a, int lda, const void* wpacked, const floa
                     ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(gelu_in) |
                       reinterpret_cast<uintptr_t>(gelu_out)) & 15) == 0,
                 "conv_gemm_gelu: ldo, Ncols multiples of 8, 16-B aligned buffers");
-  const int KGp = (KG + 3) & ~3;
-  GemmArgs g{a, lda, wpacked, bias, out, ldo, nullptr, M, Ncols, Cpad, KG, 0, 1, 1, 1, 1, KGp,
-             1 /* XCD-aware block remap */, 0, nullptr, nullptr};
+  GemmArgs g = gemm_shape(M, Ncols, Cpad, KG, 0, 1, 1, 1, lda, ldo);
+  g.a = a; g.b = wpacked; g.bias = bias; g.out = out;
   MMSEG_REQUIRE(lda % 8 == 0, "conv_gemm_gelu: lda must be a multiple of 8");
   MMSEG_REQUIRE(Cpad >= ((Ncols + (Ncols >= 64 ? 63 : 31)) / (Ncols >= 64 ? 64 : 32)) * (Ncols >= 64 ? 64 : 32),
                 "conv_gemm_gelu: packed weights must be padded to the column tile (Cpad=%d, Ncols=%d)", Cpad, Ncols);
@@ -5592,12 +5633,9 @@ int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bia
                 "conv_gemm: packed weights must be padded to the column tile (Cpad=%d, Ncols=%d)", Cpad, Ncols);
   MMSEG_REQUIRE(ksplit >= 1, "conv_gemm: ksplit >= 1");
   MMSEG_REQUIRE(ksplit == 1 || splitk_ws != nullptr, "conv_gemm: split-K needs a workspace");
-  const int KGp = (KG + 3) & ~3;
-  int kps = ((ceil_div(KGp, ksplit) + 3) / 4) * 4;
-  ksplit = ceil_div(KGp, kps);
-  GemmArgs g{a, lda, wpacked, bias, out, ldo, splitk_ws, M, Ncols, Cpad, KG, cpg_shift, D, H, W, ksplit, kps,
-             1 /* XCD-aware block remap */, mode == MODE_CONV3 ? (cin_real + 31) / 32 : 0, nullptr, nullptr, out2, ldo2,
-             split};
+  GemmArgs g = gemm_shape(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, ksplit, mode == MODE_CONV3 ? cin_real : 0);
+  g.a = a; g.b = wpacked; g.bias = bias; g.out = out; g.part = splitk_ws;
+  g.out2 = out2; g.ldo2 = ldo2; g.split = split;
   if (groups > 1) {
     g.grp_n = M / (D * H * W) / groups;
     g.w_gstride = w_gstride;
@@ -5616,11 +5654,7 @@ int conv_gemm_impl(const void* a, int lda, const void* wpacked, const float* bia
 int mmseg_conv3_norm_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                         int dtype) {
   if (dtype != MMSEG_BF16 || !knob("MMSEG_DEFER_CONV_NORM", 1)) return 0;
-  GemmArgs g{};
-  g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
-  g.D = D; g.H = H; g.W = W; g.ksplit = 1;
-  g.out = reinterpret_cast<void*>(static_cast<uintptr_t>(256));   // the caller's output is 16-B aligned (checked)
-  return brick6_selected(g, 2) ? 1 : 0;
+  return choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype, CF_NORM).kernel == GK_BRICK6;
 }
 
 // 3^3 conv forward of an A source holding the PRE-norm activation of an InstanceNorm + ReLU: the kernel stages
@@ -5632,19 +5666,14 @@ int mmseg_conv3_fwd_norm(const void* a, int lda, const float* nmean, const float
   MMSEG_REQUIRE(nmean && nrstd && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                     mmseg_conv3_norm_ok(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype),
                 "conv3_fwd_norm: unsupported shape (mmseg_conv3_norm_ok)");
-  const int KGp = (KG + 3) & ~3;
-  GemmArgs g{a, lda, wpacked, bias, out, ldo, nullptr, M, Ncols, Cpad, KG, cpg_shift, D, H, W, 1, KGp,
-             1 /* XCD-aware block remap */, 0, nmean, nrstd};
+  GemmArgs g = gemm_shape(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo);
+  g.a = a; g.b = wpacked; g.bias = bias; g.out = out; g.nmean = nmean; g.nrstd = nrstd;
   return launch_gemm<bf16_t, MODE_CONV3>(g, (hipStream_t)stream);
 }
 
 // Mixed bf16/fp8 forward (config c5): the brick6 shapes of a 3^3 conv with e4m3 operands and fp32 accumulation.
 int mmseg_conv3_fp8_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo) {
-  GemmArgs g{};
-  g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
-  g.D = D; g.H = H; g.W = W; g.ksplit = 1;
-  g.out = reinterpret_cast<void*>(static_cast<uintptr_t>(256));
-  return brick6_selected(g, 2) ? 1 : 0;
+  return choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, MMSEG_BF16, CF_FP8).kernel == GK_BRICK6;
 }
 
 int mmseg_pack_conv3_fp8(const float* w, int Co, int Ci, int Cip, int KGp, int Cpad, void* dst, float* wdq,
@@ -5666,29 +5695,17 @@ int mmseg_conv3_fwd_fp8(const void* a, int lda, const float* nmean, const float*
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                     mmseg_conv3_fp8_ok(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo),
                 "conv3_fwd_fp8: unsupported shape (mmseg_conv3_fp8_ok)");
-  const int KGp = (KG + 3) & ~3;
-  GemmArgs g{a, lda, w8, bias, out, ldo, nullptr, M, Ncols, Cpad, KG, cpg_shift, D, H, W, 1, KGp,
-             1 /* XCD-aware block remap */, 0, nmean, nrstd};
-  g.wdq = wdq;
-  launch_brick6(g, (hipStream_t)stream);
-  return mmseg::check_launch("conv3_fwd_fp8");
+  GemmArgs g = gemm_shape(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo);
+  g.a = a; g.b = w8; g.bias = bias; g.out = out; g.nmean = nmean; g.nrstd = nrstd; g.wdq = wdq;
+  return launch_gemm<bf16_t, MODE_CONV3>(g, (hipStream_t)stream);
 }
 
 // Chunks per sample of the InstanceNorm-backward partials mmseg_conv3_dgrad_in writes for this CONV3 data-gradient
 // shape (the brick6 kernel's blocks per column tile), or 0 when that kernel does not run it.
 int mmseg_conv3_dgrad_in_chunks(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
                                 int ldo, int dtype) {
-  if (dtype != MMSEG_BF16) return 0;
-  GemmArgs g{};
-  g.lda = lda; g.ldo = ldo; g.M = M; g.Ncols = Ncols; g.Cpad = Cpad; g.KG = KG; g.cpg_shift = cpg_shift;
-  g.D = D; g.H = H; g.W = W; g.ksplit = 1;
-  g.out = reinterpret_cast<void*>(static_cast<uintptr_t>(256));   // the caller's output is 16-B aligned (checked)
-  if (!brick6_selected(g, 2)) return 0;
-  const int nt_n = Ncols / 32;
-  const int per_nt = std::max(1, knob("MMSEG_BRICK4_BLOCKS", 256) / nt_n);
-  const int nb6 = (M / (D * H * W)) * (D / 4) * (H / 4) * (W / 16);
-  const int upb6 = ceil_div(nb6, std::min(per_nt, nb6));
-  return ceil_div(nb6, upb6);
+  const GemmChoice c = choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype, CF_INPART);
+  return c.kernel == GK_BRICK6 ? c.bpn : 0;
 }
 
 // CONV3 data gradient (mmseg_conv_gemm, ksplit 1, no bias) whose output dy feeds the backward of an InstanceNorm +
@@ -5701,21 +5718,13 @@ int mmseg_conv3_dgrad_in(const void* a, int lda, const void* wpacked, void* out,
   MMSEG_REQUIRE(inx && inmean && inrstd && inpart && ldinx % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                     mmseg_conv3_dgrad_in_chunks(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype) > 0,
                 "conv3_dgrad_in: unsupported shape (mmseg_conv3_dgrad_in_chunks)");
-  const int KGp = (KG + 3) & ~3;
-  GemmArgs g{a, lda, wpacked, nullptr, out, ldo, nullptr, M, Ncols, Cpad, KG, cpg_shift, D, H, W, 1, KGp,
-             1 /* XCD-aware block remap */, 0, nullptr, nullptr};
-  g.inx = inx;
-  g.ldinx = ldinx;
-  g.inmean = inmean;
-  g.inrstd = inrstd;
-  g.inpart = inpart;
-  launch_brick6(g, (hipStream_t)stream);
-  return mmseg::check_launch("conv3_dgrad_in");
+  GemmArgs g = gemm_shape(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo);
+  g.a = a; g.b = wpacked; g.out = out;
+  g.inx = inx; g.ldinx = ldinx; g.inmean = inmean; g.inrstd = inrstd; g.inpart = inpart;
+  return launch_gemm<bf16_t, MODE_CONV3>(g, (hipStream_t)stream);
 }
 
-// Number of K splits the CONV3 path wants for this shape (callers size the
-// split-K workspace, ksplit*M*Ncols floats, with it and pass it as ksplit).
-// 1 when mmseg_conv_gemm_group / mmseg_conv3_wgrad_group take this shape: the runtime-brick conv (plan kind 2)
+// 1 when mmseg_conv_gemm_group / mmseg_conv3_wgrad_group take this shape: the runtime-brick conv
 // and, for the weight gradient, the runtime-brick weight-gradient kernel (kind 3).
 // (a grouped launch takes the runtime-brick kernels; MMSEG_GROUP_FORCE_R (default on) also groups shapes that would
 // otherwise take the (4, 8, 8)-brick family -- the 24^3 / 48^3 levels: one launch over both modalities on the
@@ -5723,87 +5732,61 @@ int mmseg_conv3_dgrad_in(const void* a, int lda, const void* wpacked, void* out,
 int mmseg_conv3_group_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                          int dtype) {
   if (!knob("MMSEG_GROUP_SMALL", 1)) return 0;
-  const int ts = dtype == MMSEG_BF16 ? 2 : 4;
-  if (plan_conv3(M, Ncols, 8 << cpg_shift, D, H, W, lda, ldo, ts).kind == 2) return 1;
-  return knob("MMSEG_GROUP_FORCE_R", 1) && plan_conv3(M, Ncols, 8 << cpg_shift, D, H, W, lda, ldo, ts, true).kind == 2
-             ? 1 : 0;
+  if (choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype).kernel == GK_BRICKR) return 1;
+  return knob("MMSEG_GROUP_FORCE_R", 1) &&
+         choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype, CF_GROUPS).kernel == GK_BRICKR;
 }
 int mmseg_conv3_wgrad_group_ok(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W, int lddy,
                                int ldx, int dtype) {
   if (!knob("MMSEG_GROUP_SMALL", 1)) return 0;
-  if (plan_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, 1LL << 40).kind == 3) return 1;
+  if (choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, 1LL << 40).kind == 3) return 1;
   return knob("MMSEG_GROUP_FORCE_R", 1) &&
-                 plan_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, 1LL << 40, true).kind == 3
-             ? 1 : 0;
+         choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, 1LL << 40, 2).kind == 3;
 }
-// split count of a grouped conv (mmseg_conv_gemm_group): the runtime-brick plan's
+// split count of a grouped conv (mmseg_conv_gemm_group): the runtime-brick kernel's
 int mmseg_conv3_group_splits(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                              int dtype) {
-  const Conv3Plan p = plan_conv3(M, Ncols, 8 << cpg_shift, D, H, W, lda, ldo, dtype == MMSEG_BF16 ? 2 : 4, true);
-  return p.kind == 2 ? p.ks : 1;
+  const GemmChoice c = choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype, CF_GROUPS);
+  return c.kernel == GK_BRICKR ? c.ks_want : 1;
 }
 
+// Number of K splits the CONV3 path wants for this shape (callers size the
+// split-K workspace, ksplit*M*Ncols floats, with it and pass it as ksplit).
 int mmseg_conv3_splits(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda, int ldo,
                        int dtype) {
-  const int tsize = dtype == MMSEG_BF16 ? 2 : 4;
-  const Conv3Plan p = plan_conv3(M, Ncols, 8 << cpg_shift, D, H, W, lda, ldo, tsize);
-  if (p.kind == 2) return p.ks;
-  if (p.kind == 1) return 1;
-  // per-lane gather GEMM: enough (128 x 64|32) tiles to fill the chip
-  const int tiles = ceil_div(M, 128) * ceil_div(Ncols, Ncols >= 64 ? 64 : 32);
-  if (tiles >= 512 || KG < 32) return 1;
-  int ks = ceil_div(512, tiles);
-  if (ks > KG / 16) ks = KG / 16;
-  return ks < 1 ? 1 : ks;
+  return choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype).ks_want;
 }
 
-// Weight-gradient partials: part[ksplit][Ca][Ncols] (fp32).
+// The family name (mmseg_last_kernel()) a 3^3 conv forward / data gradient of this shape would launch with split
+// count ksplit; flags: 1 deferred norm, 2 IN-backward partials, 4 e4m3 weights, 8 grouped.
+const char* mmseg_conv3_kernel(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D, int H, int W, int lda,
+                               int ldo, int cin_real, int ksplit, int flags, int dtype) {
+  return choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, dtype, flags, ksplit, cin_real).name;
+}
+
+// Weight-gradient partials of the 1x1 and transposed-conv layers: part[ksplit][Ca][Ncols] (fp32).
 int mmseg_wgrad(const void* a, int lda, const void* b, int ldb, float* part, float* bias_part, int mode, int Ca,
                 int Ncols, int cpg_shift, long long V, int D, int H, int W, int ksplit, int dtype, void* stream) {
   MMSEG_REQUIRE(Ca % 8 == 0, "wgrad: rows (%d) must be a multiple of 8", Ca);
   MMSEG_REQUIRE(Ncols % 8 == 0, "wgrad: cols (%d) must be a multiple of 8", Ncols);
   MMSEG_REQUIRE(V < (1LL << 31), "wgrad: voxel count %lld must fit 31 bits", V);
-  // legacy entry (tap-major partials + mmseg_wgrad_reduce): brick kinds 2/3 write channel-major tiles and
-  // are reached through mmseg_conv3_wgrad only
-  int brick = mode == MODE_CONV3 ? wgrad_brick_ok(Ca, cpg_shift, D, H, W, lda, ldb, dtype) : 0;
-  if (brick > 1) brick = 1;
-  long long vps = ((V + ksplit - 1) / ksplit + 63) / 64 * 64;
-  if (brick) {
-    ksplit = brick_wgrad_splits(V, ksplit, Ca, cpg_shift, brick, D, H, W);
-  } else {
-    ksplit = (int)((V + vps - 1) / vps);
-  }
+  MMSEG_REQUIRE(mode == MODE_POINT || mode == MODE_CONVT_DGRAD,
+                "wgrad: mode %d: this entry takes the 1x1 (1) and transposed-conv (3) layers; the 3^3 weight gradient "
+                "is mmseg_conv3_wgrad", mode);
+  MMSEG_REQUIRE(ksplit >= 1, "wgrad: ksplit >= 1");
+  const long long vps = ((V + ksplit - 1) / ksplit + 63) / 64 * 64;
+  ksplit = (int)((V + vps - 1) / vps);
   WgradArgs g{a, lda, b, ldb, part, bias_part, Ca, Ncols, cpg_shift, V, D, H, W, ksplit, vps,
-              1, brick, nullptr, nullptr, 0};
+              1, 0, nullptr, nullptr, 0};
+  Conv3WgradChoice c{};
+  c.kernel = WK_GATHER;
+  c.name = mode == MODE_POINT ? "wgrad_kernel<point>" : "wgrad_kernel<convT_dgrad>";
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == MMSEG_BF16) {
-    switch (mode) {
-      case MODE_CONV3: return launch_wgrad<bf16_t, MODE_CONV3>(g, s);
-      case MODE_POINT: return launch_wgrad<bf16_t, MODE_POINT>(g, s);
-      case MODE_CONVT_DGRAD: return launch_wgrad<bf16_t, MODE_CONVT_DGRAD>(g, s);
-    }
-  } else {
-    switch (mode) {
-      case MODE_CONV3: return launch_wgrad<float, MODE_CONV3>(g, s);
-      case MODE_POINT: return launch_wgrad<float, MODE_POINT>(g, s);
-      case MODE_CONVT_DGRAD: return launch_wgrad<float, MODE_CONVT_DGRAD>(g, s);
-    }
-  }
-  mmseg::set_error("wgrad: bad mode %d", mode);
-  return 1;
+  return dtype == MMSEG_BF16 ? launch_wgrad_mode<bf16_t>(g, c, mode, s) : launch_wgrad_mode<float>(g, c, mode, s);
 }
 
 // Effective split count the wgrad launcher will use (callers size `part` with it).
 int mmseg_wgrad_splits(long long V, int ksplit) { return mmseg_wgrad_splits_impl(V, ksplit); }
-
-// Same for the CONV3 brick path (splits the list of 4x4x8 bricks).
-int mmseg_wgrad_splits_conv3(long long V, int ksplit, int Ca, int cpg_shift, int D, int H, int W, int lda, int ldb,
-                             int dtype) {
-  int kind = wgrad_brick_ok(Ca, cpg_shift, D, H, W, lda, ldb, dtype);
-  if (kind > 1) kind = 1;   // the legacy entry's kernels (see mmseg_wgrad)
-  if (!kind) return mmseg_wgrad_splits(V, ksplit);
-  return brick_wgrad_splits(V, ksplit, Ca, cpg_shift, kind, D, H, W);
-}
 
 int mmseg_wgrad_reduce(const float* part, float* grad, const float* bias_part, float* bias_grad, int Ca, int Ncols,
                        int ksplit, int cpad, int creal, int ntap, int accumulate, void* stream) {
@@ -5828,28 +5811,21 @@ int mmseg_wgrad_reduce_defer(const float* part, float* grad, const float* bias_p
 long long mmseg_conv3_wgrad_ws_floats(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W,
                                       int lddy, int ldx, int dtype) {
   const long long cap = 16LL << 20;
-  return plan_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, cap).ws;
-}
-
-// Grouped weight gradient (mmseg_conv3_wgrad_group): the plan of the whole V, its split count rounded down to a
-// multiple of `groups` (at least one split per group), never direct.
-Conv3WgradPlan plan_conv3_wgrad_grouped(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W,
-                                        int lda, int ldb, int dtype, long long ws_cap, int groups) {
-  Conv3WgradPlan p = plan_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lda, ldb, dtype, ws_cap, groups > 1);
-  if (groups <= 1) return p;
-  p.ksplit = p.ksplit / groups * groups;
-  if (p.ksplit < groups) p.ksplit = groups;
-  // one split per group (the deepest levels): each writes its group's gradient directly, as the ungrouped
-  // single-split launch does -- a reduce would only copy 2 x 28 MB there (28.8 us, r04d)
-  p.direct = p.kind >= 2 && p.ksplit == groups && Ci == Cip;
-  p.ws = p.direct ? 0 : (long long)p.ksplit * ((long long)Co * 27 * Cip + Co);
-  return p;
+  return choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, cap).ws;
 }
 
 long long mmseg_conv3_wgrad_group_ws_floats(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W,
                                             int lddy, int ldx, int groups, int dtype) {
   const long long cap = 16LL << 20;
-  return plan_conv3_wgrad_grouped(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, cap, groups).ws;
+  return choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, cap, groups).ws;
+}
+
+// The family name (mmseg_last_kernel()) the weight gradient of a 3^3 conv of this shape would launch with a
+// workspace of ws_floats; flags: 1 deferred norm, 8 grouped, 16 last 16 rows padding (phase bit 8).
+const char* mmseg_conv3_wgrad_kernel(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W,
+                                     int lddy, int ldx, long long ws_floats, int flags, int dtype) {
+  return choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, ws_floats,
+                            (flags & CF_GROUPS) ? 2 : 1, flags & CF_NORM, flags & CF_PAD16).name;
 }
 
 int conv3_wgrad_impl(const void* dy, int lddy, const void* x, int ldx, const float* nmean, const float* nrstd,
@@ -5883,7 +5859,7 @@ int mmseg_conv3_wgrad(const void* dy, int lddy, const void* x, int ldx, float* g
 int mmseg_conv3_wgrad_norm_ok(long long V, int Co, int Cip, int Ci, int cpg_shift, int D, int H, int W, int lddy,
                               int ldx, int dtype) {
   if (dtype != MMSEG_BF16 || Ci != Cip || !knob("MMSEG_DEFER_CONV_NORM", 1)) return 0;
-  return plan_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, 1LL << 40).kind == 2 ? 1 : 0;
+  return choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, 1LL << 40).kind == 2 ? 1 : 0;
 }
 
 // mmseg_conv3_wgrad with x the PRE-norm activation of an InstanceNorm + ReLU ([N][Cip] mean / rstd), applied on
@@ -5971,8 +5947,8 @@ int conv3_wgrad_impl(const void* dy, int lddy, const void* x, int ldx, const flo
                      int groups, long long grad_gstride, int bias_gstride) {
   MMSEG_REQUIRE(Co % 8 == 0 && Cip % 8 == 0 && Ci <= Cip && (8 << cpg_shift) == Cip,
                 "conv3_wgrad: Co=%d, Cip=%d must be multiples of 8, Ci=%d <= Cip, Cip = 8 << cpg_shift", Co, Cip, Ci);
-  const Conv3WgradPlan p = plan_conv3_wgrad_grouped(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, ws_floats,
-                                                    groups);
+  const Conv3WgradChoice p = choose_conv3_wgrad(V, Co, Cip, Ci, cpg_shift, D, H, W, lddy, ldx, dtype, ws_floats, groups,
+                                                nmean != nullptr, (phase & 8) != 0);
   MMSEG_REQUIRE(!nmean || p.kind == 2, "conv3_wgrad: a deferred norm needs the brick2 weight-gradient kernel");
   MMSEG_REQUIRE(groups <= 1 || p.kind == 3, "conv3_wgrad_group: only the runtime-brick weight gradient is grouped");
   MMSEG_REQUIRE(p.ws <= ws_floats && (p.ws == 0 || ws != nullptr), "conv3_wgrad: workspace of %lld floats < %lld",
@@ -5988,25 +5964,21 @@ int conv3_wgrad_impl(const void* dy, int lddy, const void* x, int ldx, const flo
               1, p.kind, p.direct ? grad : nullptr, p.direct ? bias_grad : nullptr,
               accumulate, wgrad_kchunks(Cip, Ci), nmean, nrstd};
   hipStream_t s = (hipStream_t)stream;
-  g.groups = groups > 1 ? groups : 0;
-  g.pad16 = (phase & 8) ? 1 : 0;
-  // the row-slab kernel writes fragment-native partials only (2 co tiles of 16)
-  const int fmt = wgrad_row_ok(g, dtype == MMSEG_BF16 ? 2 : 4) ? 2
-                  : wgrad_dma_mt(g, dtype == MMSEG_BF16 ? 2 : 4);
-  g.frag = fmt > 0;
+  g.frag = p.fmt > 0;
   g.groups = groups > 1 ? groups : 0;
   g.grad_gstride = grad_gstride;
   g.bias_gstride = bias_gstride;
   g.pad16 = (phase & 8) ? 1 : 0;
   g.grad_ld = p.direct ? 27 * Ci : 0;
   if (phase & 1) {
-    const int rc = dtype == MMSEG_BF16 ? launch_wgrad<bf16_t, MODE_CONV3>(g, s) : launch_wgrad<float, MODE_CONV3>(g, s);
+    const int rc = dtype == MMSEG_BF16 ? launch_wgrad_mode<bf16_t>(g, p, MODE_CONV3, s)
+                                       : launch_wgrad_mode<float>(g, p, MODE_CONV3, s);
     if (rc) return rc;
   }
   if (p.direct || !(phase & 2)) return 0;
   const int ng = groups > 1 ? groups : 1;
   WReduceArgs r{part, grad, bpart, bias_grad, Co, ncols, p.ksplit / ng, Cip, Ci, 27, accumulate, p.kind >= 2 ? 1 : 0,
-                fmt, wgrad_nchunk(cpg_shift, g.kchunks), grad_gstride, bias_gstride};
+                p.fmt, wgrad_nchunk(cpg_shift, g.kchunks), grad_gstride, bias_gstride};
   r.vec4 = r.chmajor && !r.frag_mt && ((uintptr_t)grad & 15) == 0 &&
            (ng == 1 || grad_gstride % 4 == 0) && r.Ncols % 4 == 0 && ((long long)r.creal * r.ntap) % 4 == 0;
   if (phase & 4) {   // deferred: summed by the next mmseg_wgrad_reduce_flush on this stream

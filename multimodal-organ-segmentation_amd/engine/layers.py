@@ -35,7 +35,7 @@ def _own_part(obj, rt: Runtime, nfloats: int) -> torch.Tensor:
     return rt.own_part(obj, nfloats)
 
 
-def _gemm_name(rt: Runtime, ncols: int, mode: str):
+def _gemm_name(rt: Runtime):
     """Timer family = the kernel the library actually launched (same name as in rocprofv3 traces)."""
     return lambda: f"{rt.lib.mmseg_last_kernel().decode()}[{'bf16' if rt.code else 'f32'}]"
 
@@ -78,10 +78,7 @@ class Packer:
         # None: unknown -- the next pack writes them
         self.fresh = None
         self._adam = None
-        self.per_layer = []
         self.table = self.gtable = None
-        if self.per_layer:
-            return
         nbytes = rt.lib.mmseg_pack3_desc_bytes()
         blob, begin, n = bytearray(), 0, 0
         dgrad = {d[0]: d for d in descs if d[2] in (1, 6)}
@@ -129,7 +126,7 @@ class Packer:
         2), each element exactly once.  None when some weight's images do not fit those kinds (the captured step
         then keeps the pack in its forward)."""
         import struct
-        if self.per_layer or not self.descs:
+        if not self.descs:
             return None
         base, numel = flat.flat.data_ptr(), flat.numel
         groups = {}
@@ -197,8 +194,6 @@ class Packer:
             L.mmseg_pack_conv3_batched(ptr(self.table), self.n, self.nblocks, code, s)
         if self.gtable is not None:
             L.mmseg_pack_weights_batched(ptr(self.gtable), self.gn, self.gtotal, code, s)
-        for d in self.per_layer:
-            L.mmseg_pack_weight(*d, code, s)
 
 
 def _wgrad_ksplit(rows: int, ncols: int, V: int) -> int:
@@ -340,7 +335,7 @@ class Conv3:
         ks = self.rt.lib.mmseg_conv3_splits(M, nc, self.Cpad, self.KG, self.cpg_shift, x.D, x.H, x.W, x.ld, y.ld,
                                             self.rt.code)
         ws = self.rt.ws(ks * M * nc) if ks > 1 else None
-        with TIMER.region(_gemm_name(self.rt, nc, "conv3"), flops=2.0 * M * self.Co * 27 * self.Ci,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Co * 27 * self.Ci,
                           nbytes=_io_bytes(self.rt, M, self.Cip, self.Co, 27 * self.Cip * self.Co)):
             # (an output owning its padded rows is written whole: Act.wcols, mmseg_conv_gemm_zw)
             self.rt.lib.mmseg_conv_gemm_zw(x.ptr, x.ld, ptr(self.wf), ptr(self.conv.bias), y.ptr, y.ld, ptr(ws),
@@ -363,7 +358,7 @@ class Conv3:
         if self.fp8_ok(x, y):
             self.fwd_fp8(x, y, norm=(mean, rstd))
             return
-        with TIMER.region(_gemm_name(self.rt, self.ncols_f, "conv3"), flops=2.0 * x.N * x.V * self.Co * 27 * self.Ci,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * x.N * x.V * self.Co * 27 * self.Ci,
                           nbytes=_io_bytes(self.rt, x.N * x.V, self.Cip, self.Co, 27 * self.Cip * self.Co)):
             self.rt.lib.mmseg_conv3_fwd_norm(x.ptr, x.ld, ptr(mean), ptr(rstd), ptr(self.wf), ptr(self.conv.bias),
                                              y.ptr, y.ld, x.N * x.V, self.ncols_f, self.Cpad, self.KG,
@@ -453,7 +448,7 @@ class Conv3:
         pad16 = 8 if (self.wg_stage is not None and rows - self.Co == 16) else 0
 
         def wkernel(s1):
-            with TIMER.region(_gemm_name(self.rt, 0, "conv3"), flops=2.0 * V * self.Co * 27 * self.Ci,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Co * 27 * self.Ci,
                               nbytes=_io_bytes(self.rt, V, self.Cip, self.Co, 27 * self.Cip * self.Co, 4)):
                 L.mmseg_conv3_wgrad_ex(*args, 1 | pad16, code, s1)
 
@@ -482,7 +477,7 @@ class Conv3:
             nc = self.ncols_d
             ks = L.mmseg_conv3_splits(M, nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, dy.ld, d0.ld, code)
             ws = self.rt.ws(ks * M * nc) if ks > 1 else None
-            with TIMER.region(_gemm_name(self.rt, nc, "conv3"), flops=2.0 * M * self.Co * 27 * self.Ci,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Co * 27 * self.Ci,
                               nbytes=_io_bytes(self.rt, M, self.Co, self.Cip, 27 * self.Cip * self.Co)):
                 nch = 0
                 if inp is not None and not split and ks == 1 and os.environ.get("MMSEG_DGRAD_IN_PART", "1") != "0":
@@ -543,7 +538,7 @@ class ConvT2:
         ncols = 8 * self.Co
         ks = _gemm_ksplit(M, ncols, self.KG)
         ws = self.rt.ws(ks * M * ncols) if ks > 1 else None
-        with TIMER.region(_gemm_name(self.rt, 0, "convT"), flops=2.0 * M * self.Ci * 8 * self.Co,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Ci * 8 * self.Co,
                           nbytes=_io_bytes(self.rt, M, self.Ci, 8 * self.Co, 8 * self.Ci * self.Co)):
             self.rt.lib.mmseg_conv_gemm(x.ptr, x.ld, ptr(self.wf), ptr(self.up.bias), y.ptr, y.ld, ptr(ws),
                                         MODE_CONVT_FWD, M, ncols, self.Cpad, self.KG, 0, x.D, x.H, x.W, ks,
@@ -563,7 +558,7 @@ class ConvT2:
         nfl = max(ks * self.Ci * ncols + (ks * ncols if fused_bias else 0), 256 * self.Co)
         part = _own_part(self, self.rt, nfl) if defer else self.rt.ws(nfl)
         bpart = part.data_ptr() + ks * self.Ci * ncols * 4 if fused_bias else None
-        with TIMER.region(_gemm_name(self.rt, 0, "convT"), flops=2.0 * V * self.Ci * 8 * self.Co,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * 8 * self.Co,
                           nbytes=_io_bytes(self.rt, V, self.Ci, 8 * self.Co, 8 * self.Ci * self.Co, 4)):
             L.mmseg_wgrad(x.ptr, x.ld, dy.ptr, dy.ld, ptr(part), bpart, MODE_CONVT_DGRAD, self.Ci, ncols,
                           self.dshift, V, x.D, x.H, x.W, ks, code, s)
@@ -579,7 +574,7 @@ class ConvT2:
         if dx is not None:
             ks = _gemm_ksplit(V, self.Ci, self.KGd)
             ws = self.rt.ws(ks * V * self.Ci) if ks > 1 else None
-            with TIMER.region(_gemm_name(self.rt, 0, "convT"), flops=2.0 * V * self.Ci * 8 * self.Co,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * 8 * self.Co,
                               nbytes=_io_bytes(self.rt, V, 8 * self.Co, self.Ci, 8 * self.Ci * self.Co)):
                 L.mmseg_conv_gemm(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, ptr(ws), MODE_CONVT_DGRAD, V,
                                   self.Ci, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, ks, code, s)
@@ -607,7 +602,7 @@ class Point:
 
     def fwd(self, x: Act, y: Act):
         M = x.N * x.V
-        with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * M * self.Ci * self.Co,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Ci * self.Co,
                           nbytes=_io_bytes(self.rt, M, self.Ci, self.Co, self.Ci * self.Co)):
             self.rt.lib.mmseg_conv_gemm(x.ptr, x.ld, ptr(self.wf), ptr(self.conv.bias), y.ptr, y.ld, None, MODE_POINT,
                                         M, self.Co, self.Cpad, self.KG, 0, x.D, x.H, x.W, 1, self.rt.code,
@@ -621,7 +616,7 @@ class Point:
         nfl = ks * self.Co * self.Ci + ks * self.Co
         part = _own_part(self, self.rt, nfl) if defer else self.rt.ws(nfl)
         bpart = part.data_ptr() + ks * self.Co * self.Ci * 4
-        with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * V * self.Ci * self.Co,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * self.Co,
                           nbytes=_io_bytes(self.rt, V, self.Ci, self.Co, self.Ci * self.Co, 4)):
             L.mmseg_wgrad(dy.ptr, dy.ld, x.ptr, x.ld, ptr(part), bpart, MODE_POINT, self.Co, self.Ci, 0, V, x.D, x.H,
                           x.W, ks, code, s)
@@ -630,7 +625,7 @@ class Point:
             self.Ci, ks, self.Ci, self.Ci, 1, int(accumulate), s)
         self.flat.mark(self.conv.weight, self.conv.bias)
         if dx is not None:
-            with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * V * self.Ci * self.Co,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * self.Co,
                               nbytes=_io_bytes(self.rt, V, self.Co, self.Ci, self.Ci * self.Co)):
                 L.mmseg_conv_gemm(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, None, MODE_POINT, V, self.Ci,
                                   self.Cpad_d, self.KGd, 0, x.D, x.H, x.W, 1, code, s)
@@ -822,7 +817,7 @@ class ConvGroup:
         M, nc = x.N * x.V, c.ncols_f
         ks = L.mmseg_conv3_group_splits(M, nc, c.Cpad, c.KG, c.cpg_shift, x.D, x.H, x.W, x.ld, y.ld, self.rt.code)
         ws = self.rt.ws(ks * M * nc) if ks > 1 else None
-        with TIMER.region(_gemm_name(self.rt, nc, "conv3"), flops=2.0 * M * c.Co * 27 * c.Ci,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * c.Co * 27 * c.Ci,
                           nbytes=_io_bytes(self.rt, M, c.Cip, c.Co, self.G * 27 * c.Cip * c.Co)):
             L.mmseg_conv_gemm_group(x.ptr, x.ld, ptr(c.wf), ptr(c.conv.bias), y.ptr, y.ld, ptr(ws), MODE_CONV3, M, nc,
                                     c.Cpad, c.KG, c.cpg_shift, x.D, x.H, x.W, ks, c.kreal_f, self.G, self.w_gs,
@@ -842,7 +837,7 @@ class ConvGroup:
         args = (dy.ptr, dy.ld, x.ptr, x.ld, gw, gb, c.Co, c.Cip, c.Ci, c.cpg_shift, V, x.D, x.H, x.W, ptr(ws), wsf,
                 int(accumulate), self.G, self.gw_gs, self.gb_gs)
         def wkernel(s1):
-            with TIMER.region(_gemm_name(self.rt, 0, "conv3"), flops=2.0 * V * c.Co * 27 * c.Ci,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * c.Co * 27 * c.Ci,
                               nbytes=_io_bytes(self.rt, V, c.Cip, c.Co, self.G * 27 * c.Cip * c.Co, 4)):
                 L.mmseg_conv3_wgrad_group(*args, 1, code, s1)
 
@@ -859,7 +854,7 @@ class ConvGroup:
             M, nc = V, c.ncols_d
             ks = L.mmseg_conv3_group_splits(M, nc, c.Cpad_d, c.KGd, c.dshift, x.D, x.H, x.W, dy.ld, dx.ld, code)
             ws2 = self.rt.ws(ks * M * nc) if ks > 1 else None
-            with TIMER.region(_gemm_name(self.rt, nc, "conv3"), flops=2.0 * M * c.Co * 27 * c.Ci,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * c.Co * 27 * c.Ci,
                               nbytes=_io_bytes(self.rt, M, c.Co, c.Cip, self.G * 27 * c.Cip * c.Co)):
                 L.mmseg_conv_gemm_group(dy.ptr, dy.ld, ptr(c.wd), None, dx.ptr, dx.ld, ptr(ws2), MODE_CONV3, M, nc,
                                         c.Cpad_d, c.KGd, c.dshift, x.D, x.H, x.W, ks, c.kreal_d, self.G, self.wd_gs, 0,

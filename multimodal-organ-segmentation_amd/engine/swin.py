@@ -127,7 +127,7 @@ class Lin:
         (mmseg_conv_gemm_gelu) when it runs without split-K, else the GEMM + mmseg_gelu_fwd -- bitwise the same."""
         L = self.rt.lib
         if _gemm_ksplit(M, self.Co, self.KG) == 1 and _res_fuse():
-            with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * M * self.Ci * self.Co,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Ci * self.Co,
                               nbytes=_io_bytes(self.rt, M, self.Cip, 2 * self.Co, self.Ci * self.Co)):
                 L.mmseg_conv_gemm_gelu(ptr(x), ldx, ptr(self.wf), ptr(self.b), ptr(h), self.Co, None, ptr(g), 1, M,
                                        self.Co, self.Cpad, self.KG, self.rt.code, self.rt.stream)
@@ -149,7 +149,7 @@ class Lin:
         fuse = res is not None and ks == 1 and _res_fuse()
         out = y if res is None or fuse else torch.empty(M * ldy, dtype=self.rt.dtype, device=self.rt.device)
         ws = self.rt.ws(ks * M * nc) if ks > 1 else None
-        with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * M * self.Ci * self.Co,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Ci * self.Co,
                           nbytes=_io_bytes(self.rt, M, self.Cip, self.Co, self.Ci * self.Co)):
             if fuse:
                 L.mmseg_conv_gemm_res(ptr(x), ldx, ptr(self.wf), ptr(self.b), ptr(res), ldy, ptr(y), ldy, M, self.Co,
@@ -176,7 +176,7 @@ class Lin:
         nfl = ks * self.Co * self.Cip + ks * self.Co + 4
         part = _own_part(self, self.rt, nfl) if defer else self.rt.ws(nfl)
         bpart = part.data_ptr() + round_up(ks * self.Co * self.Cip, 4) * 4 if self.b is not None else None
-        with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * M * self.Ci * self.Co,
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Ci * self.Co,
                           nbytes=_io_bytes(self.rt, M, self.Cip, self.Co, self.Ci * self.Co, 4)):
             L.mmseg_wgrad(ptr(dy), lddy, ptr(x), ldx, ptr(part), bpart, MODE_POINT, self.Co, self.Cip, 0, M, 1, 1, 1,
                           ks, code, s)
@@ -193,7 +193,7 @@ class Lin:
                 raise ValueError("Lin.bwd(dx_add): the residual epilogue needs the unsplit GEMM")
             ws = self.rt.ws(kd * M * ncd) if kd > 1 else None
             gelu_fused = gelu_h is not None and kd == 1 and _res_fuse()
-            with TIMER.region(_gemm_name(self.rt, 0, "point"), flops=2.0 * M * self.Ci * self.Co,
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Ci * self.Co,
                               nbytes=_io_bytes(self.rt, M, self.Co, self.Ci, self.Ci * self.Co)):
                 if gelu_fused:
                     if dx_add or ncd != self.Ci or lddx != self.Ci:

@@ -58,6 +58,8 @@ def test_conv3_fp8_matches_quantized_reference(dev, norm, shape):
     layer.fwd_fp8(xa, ya, norm=(mean, rstd) if norm else None)
     torch.cuda.synchronize()
     assert rt.lib.mmseg_last_kernel().decode() == "conv3_brick6_kernel<BN32,F8>"
+    assert rt.lib.mmseg_conv3_kernel(N * D * H * W, 32, layer.Cpad, layer.KG, layer.cpg_shift, D, H, W, xa.ld, ya.ld, 0, 1,
+                                     4 | (1 if norm else 0), 1).decode() == "conv3_brick6_kernel<BN32,F8>"
     out = from_ndhwc(ya.buf, N, 32, D, H, W).double().cpu()
     # reference: the kernel's staged values (bf16 input, optional fp32 norm + ReLU) and weights, e4m3-rounded
     xb = x.to(torch.bfloat16).float().cpu()

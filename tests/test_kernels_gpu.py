@@ -100,6 +100,14 @@ def test_conv3_kernel_variants(dev, dtype, knobs, cin, cout, shape, monkeypatch)
     _check_conv3(dev, dtype, cin, cout, shape)
 
 
+def _planned_fwd(layer, x, y):
+    """The kernel the library's planning query (mmseg_conv3_kernel) names for layer.fwd(x, y)."""
+    L, M = lib(), x.N * x.V
+    shape = (M, layer.ncols_f, layer.Cpad, layer.KG, layer.cpg_shift, x.D, x.H, x.W, x.ld, y.ld)
+    ks = L.mmseg_conv3_splits(*shape, layer.rt.code)
+    return L.mmseg_conv3_kernel(*shape, layer.kreal_f, ks, 0, layer.rt.code).decode()
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cin,cout,shape,extra,kernel", [
     (64, 64, (2, 8, 16, 8), {"MMSEG_BRICK2_MINBLK": "0"}, "conv3_brick2_kernel<BN64,ZW1>"),
@@ -135,6 +143,7 @@ def test_b32_halo_staging(dev, dtype, cin, cout, shape, extra, kernel, monkeypat
         layer.fwd(xa, ya)
         torch.cuda.synchronize()
         assert lib().mmseg_last_kernel().decode().startswith(kernel)
+        assert _planned_fwd(layer, xa, ya) == lib().mmseg_last_kernel().decode()
         dxa = rt.act(N, D, H, W, cin)
         layer.bwd(xa, _act(dy, dtype), dxa, accumulate=False)
         torch.cuda.synchronize()
@@ -585,6 +594,8 @@ def test_wgrad_dma_fragment_partials(dev, cin, cout, shape, accumulate):
         L.mmseg_conv3_wgrad(ptr(dy), cout, ptr(x), cin, ptr(gw), ptr(gb), cout, cin, cin, shift, V, D, H, W,
                             ptr(ws), wsf, accumulate, 1, stream_handle())
         assert L.mmseg_last_kernel().decode().startswith("wgrad_dma_kernel")
+        assert L.mmseg_conv3_wgrad_kernel(V, cout, cin, cin, shift, D, H, W, cout, cin, wsf, 0,
+                                          1).decode() == L.mmseg_last_kernel().decode()
         torch.cuda.synchronize()
         out.append((gw, gb))
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
@@ -747,6 +758,8 @@ def test_wgrad_pad16_rows_bitwise(dev, cip, ci, shape, accumulate, monkeypatch):
                 accumulate)
         assert L.mmseg_conv3_wgrad_ex(*args, phase & ~2, 1, stream_handle()) == 0   # the kernel
         assert L.mmseg_last_kernel().decode() == "wgrad_dma_kernel<CO64>"
+        assert L.mmseg_conv3_wgrad_kernel(V, co, cip, ci, shift, D, H, W, co, cip, wsf, 16 if phase & 8 else 0,
+                                          1).decode() == "wgrad_dma_kernel<CO64>"
         assert L.mmseg_conv3_wgrad_ex(*args, 2, 1, stream_handle()) == 0            # its split reduce
         torch.cuda.synchronize()
         out[phase] = (gw.view(co, -1), gb)
@@ -781,6 +794,7 @@ def test_conv3_few_brick_units_take_runtime_brick(dev, dtype, cin, cout, shape, 
     layer.fwd(xa, ya)
     torch.cuda.synchronize()
     assert lib().mmseg_last_kernel().decode().startswith("conv3_brickr_kernel")
+    assert _planned_fwd(layer, xa, ya) == lib().mmseg_last_kernel().decode()
     xd = _q(x, dtype).requires_grad_(True)
     wd = _q(conv.weight, dtype).requires_grad_(True)
     ref = F.conv3d(xd, wd, padding=1)
@@ -830,6 +844,8 @@ def test_wgrad_row_kernel(dev, cin, shape, accumulate, norm, monkeypatch):
                                      ptr(ws), wsf, accumulate, 1, stream_handle())
         assert rc == 0, L.mmseg_last_error()
         name = L.mmseg_last_kernel().decode()
+        assert L.mmseg_conv3_wgrad_kernel(V, cout, cin, cin, shift, D, H, W, cout, cin, wsf, 1 if norm else 0,
+                                          1).decode() == name
         torch.cuda.synchronize()
         return gw, gb, name
 
