@@ -21,14 +21,13 @@
 // wgrad (dW = sum over voxels) runs as a second kernel with K = voxels: both
 // operands are staged through LDS transposed (channel-major) and reduced in a
 // fixed-order split-K pass, so weight gradients are bitwise deterministic.
-#include "mmseg_common.h"
+#include "conv_common.h"
 
 #include <stdlib.h>
 
 #include <algorithm>
 #include <type_traits>
 #include <cstdio>
-#include <vector>
 
 namespace {
 
@@ -39,131 +38,6 @@ int knob(const char* name, int dflt) {
 }
 
 enum GatherMode { MODE_CONV3 = 0, MODE_POINT = 1, MODE_CONVT_FWD = 2, MODE_CONVT_DGRAD = 3 };
-
-// Block timeline probe (diagnostics, built only with -DMMSEG_TIMING_PROBES; tools/convbench.py --probe).
-// Per block b < PROBE_NB: [realtime start, realtime end, memtime start, memtime end, HW_ID, XCC_ID, -, -];
-// then for blocks < 32, every wave's lane 0 records up to 64 memtime stamps (PROBE_T) at phase boundaries.
-#ifdef MMSEG_TIMING_PROBES
-constexpr int PROBE_NB = 16384;
-__device__ long long* g_probe = nullptr;
-__device__ __forceinline__ void probe_block(bool end) {
-  long long* p = g_probe;
-  if (p && threadIdx.x == 0 && blockIdx.x < PROBE_NB) {
-    p += 8LL * blockIdx.x;
-    p[end ? 1 : 0] = (long long)__builtin_amdgcn_s_memrealtime();
-    p[end ? 3 : 2] = (long long)__builtin_amdgcn_s_memtime();
-    if (!end) {
-      p[4] = (long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
-      p[5] = (long long)(unsigned)__builtin_amdgcn_s_getreg((15 << 11) | 20);   // HW_REG_XCC_ID
-    }
-  }
-}
-__device__ __forceinline__ void probe_stamp(int& k) {
-  long long* p = g_probe;
-  if (p && (threadIdx.x & 63) == 0 && blockIdx.x < 32 && k < 64)
-    p[8LL * PROBE_NB + ((blockIdx.x * 16 + (threadIdx.x >> 6)) * 64) + k] = (long long)__builtin_amdgcn_s_memtime();
-  ++k;
-}
-#define PROBE_BLOCK(e) probe_block(e)
-#define PROBE_T() probe_stamp(probe_k)
-#define PROBE_DECL() int probe_k = 0
-#else
-#define PROBE_BLOCK(e)
-#define PROBE_T()
-#define PROBE_DECL()
-#endif
-
-struct GemmArgs {
-  const void* a;  int lda;   // A source (NDHWC)
-  const void* b;             // packed weights [KGp][Cpad][8]
-  const float* bias;         // per output channel, or null
-  void* out;      int ldo;   // output (NDHWC) for ksplit == 1
-  float* part;               // [ksplit][M][Ncols] fp32 partials for ksplit > 1
-  int M, Ncols, Cpad, KG, cpg_shift;
-  int D, H, W;               // row grid
-  int ksplit, kg_per_split;  // k-groups per split (multiple of 4)
-  int swz;                   // XCD-aware block remap
-  int kchunks;               // CONV3 brick kernels: 32-channel input chunks holding real channels (0 = all);
-                             // the packed weights of the rest are zero (channel-padded K side), so they are skipped
-  // deferred InstanceNorm + ReLU of the A source (brick6 only, mmseg_conv3_fwd_norm): A holds the PRE-norm
-  // activation, the kernel stages relu((a - nmean[n][c]) * nrstd[n][c]) rounded to T (in_relu_apply's values)
-  const float* nmean;
-  const float* nrstd;
-  // split output (mmseg_conv_gemm_split): columns >= split go to out2 (column - split, row pitch ldo2).  The
-  // decoder's first-conv data gradient writes d(upsampled) and d(skip) as two dense tensors instead of one
-  // [voxel][2F] tensor whose halves every later reader fetched at half a cache line per voxel.
-  void* out2;
-  int ldo2, split;
-  // InstanceNorm-backward partials of the output (brick6 data gradient only, mmseg_conv3_dgrad_in): the output is
-  // the gradient dy of an InstanceNorm + ReLU whose PRE-norm input is inx (pitch ldinx, statistics inmean /
-  // inrstd [N][Ncols]); the kernel also writes inpart[n][block][col][2] = (sum g, sum g xhat), g = dy [xhat > 0]
-  const void* inx;
-  int ldinx;
-  const float* inmean;
-  const float* inrstd;
-  float* inpart;
-  // fp8 forward (brick6 F8, mmseg_conv3_fwd_fp8): b holds e4m3 weights w * s[co] (s = 448 / max |w[co]|), wdq[co] =
-  // 1 / s[co] restores the scale in the epilogue; the staged activations are e4m3 at unit scale
-  const float* wdq;
-  // grouped launch (mmseg_conv_gemm_group, runtime-brick kernel only): the samples are grp_n-sample groups with
-  // their own weights / bias -- group gi reads b + gi * w_gstride (elements) and bias + gi * b_gstride; the M
-  // modality encoders' small levels run as ONE launch over M x N samples
-  int grp_n;
-  long long w_gstride;
-  int b_gstride;
-  // residual epilogue (MODE_POINT, ksplit 1, vector stores; mmseg_conv_gemm_res): out = round(round(acc + bias) +
-  // res), the values of the GEMM followed by mmseg_add(res, out) -- a residual sum without its own pass (res may
-  // alias out)
-  const void* res;
-  int ldres;
-  // whole-row output hint (brick2 kernels; others ignore it): the last column tile also writes zeros into columns
-  // [Ncols, zcols) (<= Ncols + BN) of the output rows -- SwinUNETR's 48 / 96-column outputs at pitch 64 / 128 are
-  // then written in whole 128-B lines (partial-line writes ran at ~60 % of the whole-row rate, r05k)
-  int zcols;
-  // token-GEMM epilogue (MODE_POINT, ksplit 1, vector stores; mmseg_conv_gemm_gelu): epi 1 = GELU forward, out = h
-  // (the pre-activation the backward reads) and aux_out = gelu(h); epi 2 = GELU backward, out = round(round(acc) *
-  // gelu'(aux)) with aux = h -- the values of the GEMM followed by mmseg_gelu_fwd / mmseg_gelu_bwd (pitch ldo)
-  int epi;
-  const void* aux;
-  void* aux_out;
-};
-
-// Output element (row voxel, column) of a GEMM (split-aware; split is a multiple of 8).
-template <typename T>
-__device__ __forceinline__ T* out_at(const GemmArgs& g, long long vox, int col) {
-  if (g.out2 && col >= g.split) return reinterpret_cast<T*>(g.out2) + vox * g.ldo2 + (col - g.split);
-  return reinterpret_cast<T*>(g.out) + vox * g.ldo + col;
-}
-
-// The deferred norm of 8 staged channels: relu((v - mu) * rs) rounded to T, in_relu_apply's operations.
-template <typename T>
-__device__ __forceinline__ void norm_relu8(V8<T>& v, const float* mu, const float* rs) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float h = (v.get(j) - mu[j]) * rs[j];
-    v.set(j, h > 0.f ? h : 0.f);
-  }
-}
-
-// 32-channel K chunks a CONV3 brick kernel iterates: all of the (power-of-two) A source's, or only the
-// leading ones that hold real channels.
-__host__ __device__ __forceinline__ int gemm_nchunk(const GemmArgs& g) {
-  const int n = (8 << g.cpg_shift) / 32;
-  return (g.kchunks > 0 && g.kchunks < n) ? g.kchunks : n;
-}
-
-template <typename T>
-__device__ __forceinline__ void mfma_step(f32x4& acc, const V8<T>& a, const V8<T>& b);
-
-template <>
-__device__ __forceinline__ void mfma_step<bf16_t>(f32x4& acc, const V8<bf16_t>& a, const V8<bf16_t>& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mfma_step<float>(f32x4& acc, const V8<float>& a, const V8<float>& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
 
 // Per-lane row descriptor.
 struct RowInfo {
@@ -614,8 +488,6 @@ struct Brick2Layout {
   static constexpr int RZ = H2_Y * RY;                 // quads per halo z-plane
 };
 
-__device__ __forceinline__ int w2_swz(int col) { return ((col >> 3) & 1) << 1; }
-
 template <typename T>
 __device__ __forceinline__ void buf_load_v8(V8<T>& v, __amdgpu_buffer_rsrc_t r, uint32_t off);
 
@@ -865,31 +737,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void conv3_brick2_kern
 //   * the MFMA computes the transposed tile W^T X (A and B swapped), so a lane
 //     holds 4 consecutive output channels of one voxel: bias, bf16 packing and
 //     an 8-B global store straight from the accumulators, no LDS epilogue.
-template <typename T>
-__device__ __forceinline__ void buf_load_v8(V8<T>& v, __amdgpu_buffer_rsrc_t r, uint32_t off);
-template <>
-__device__ __forceinline__ void buf_load_v8<bf16_t>(V8<bf16_t>& v, __amdgpu_buffer_rsrc_t r, uint32_t off) {
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
-  const i32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  v.v = __builtin_bit_cast(bf16x8, t);
-}
-// The whole vector is bit-cast at once.  Casting element by element (__builtin_bit_cast(float, a[j])) is
-// miscompiled by hipcc (ROCm 7.2, gfx950): the b128 loads were narrowed to buffer_load_dword and element 0 was
-// copied into all four registers (v173..v175 = v172 in the disassembly), which is why the fp32 instantiation
-// of the 32-bit staging gave wrong results in r02 (tests/test_kernels_gpu.py::test_b32_halo_staging).
-template <>
-__device__ __forceinline__ void buf_load_v8<float>(V8<float>& v, __amdgpu_buffer_rsrc_t r, uint32_t off) {
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
-  const f32x4v a = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-  const f32x4v b = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, off + 16, 0, 0));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v.v[j] = a[j];
-    v.v[4 + j] = b[j];
-  }
-}
-
 // Measured and removed (round 6 knob pruning; numbers in DESIGN): a double-buffered weight stage (1 % slower),
 // the next halo chunk loaded at the first stage of the current one (4 % slower on the bench), unconditional
 // clamped weight loads, and sched_group_barrier interleaving of the fragment reads (8-13 % slower).
@@ -1121,31 +968,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void conv3_brick3_kern
 // the LDS read stream, not latency, barriers or the halo loads, is what bounds this kernel.
 // Requirements (host): bf16, one 32-channel K chunk, Ncols % 32 == 0, D % 4, H % 8, W % 8.
 
-// MFMA with the weight fragment pinned to the accumulator file: hipcc otherwise keeps the 216 weight
-// registers in VGPRs and, short of VGPRs, issues each tap's LDS reads just before their MFMAs.  The asm is one
-// opaque instruction to hipcc: it inserts the lgkmcnt waits for x, but no MFMA hazard padding, which
-// brick4_fence / brick4_wfence supply where the accumulators are read and after the weights are written.
-__device__ __forceinline__ void mfma_aw(f32x4& acc, const bf16x8& w, const bf16x8& x) {
-  asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(w), "v"(x));
-}
-// e4m3 x e4m3 -> f32 (K = 32: a lane holds 8 fp8 = 8 bytes of A and of B, the bf16 form's lane map)
-__device__ __forceinline__ void mfma_aw8(f32x4& acc, const long& w, const long& x) {
-  asm("v_mfma_f32_16x16x32_fp8_fp8 %0, %1, %2, %0" : "+a"(acc) : "a"(w), "v"(x));
-}
-__device__ __forceinline__ void mfma_aw80(f32x4& acc, const long& w, const long& x) {
-  asm("v_mfma_f32_16x16x32_fp8_fp8 %0, %1, %2, 0" : "=a"(acc) : "a"(w), "v"(x));
-}
-// first MFMA of an accumulation chain: C = 0 (no accumulator zeroing per brick)
-__device__ __forceinline__ void mfma_aw0(f32x4& acc, const bf16x8& w, const bf16x8& x) {
-  asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc) : "a"(w), "v"(x));
-}
-__device__ __forceinline__ void brick4_fence(f32x4& a, f32x4& b) {
-  asm volatile("s_nop 7\n\ts_nop 7" : "+a"(a), "+a"(b));
-}
-__device__ __forceinline__ void brick4_wfence(bf16x8& a, bf16x8& b) {
-  asm volatile("s_nop 2" : "+a"(a), "+a"(b));
-}
-
 __global__ __launch_bounds__(256, 1) void conv3_brick4_kernel(GemmArgs g, int upb, int blocks_per_nt) {
   using T = bf16_t;
   using L = Brick2Layout<T>;
@@ -1303,422 +1125,6 @@ __global__ __launch_bounds__(256, 1) void conv3_brick4_kernel(GemmArgs g, int up
   }
 }
 
-// ------------------------------------------------- brick conv v6 (3^3, bf16, Cin = 32, Co tile 32)
-// brick4 with the A-read stream halved.  A row tile is 16 consecutive x voxels of ONE y row (brick 4 z x
-// 4 y x 16 x, one z plane per wave), so the fragment of row tile i at tap ky is the fragment of halo row
-// i + ky: per (kz, kx) the 12 (ky, i) fragments are 6 distinct halo rows, read once and used by 24 MFMAs
-// (0.25 ds_read_b128 per MFMA instead of 0.5).  Halo image: voxel = 4 quads of 8 channels, the quad of
-// channel group kg at slot kg ^ (((hx >> 2) & 1) << 1), which makes the 16-lane groups of ds_read_b128
-// conflict-free for all three kx shifts; rows of 18 voxels, no padding.
-// Requirements (host): bf16, one 32-channel K chunk, Ncols % 32 == 0, D % 4, H % 4, W % 16.
-// Its predecessor v5 (same layout, same arithmetic, bitwise the same outputs; removed) measured ~8,000 cycles per
-// brick against 3,456 of MFMA issue (r03s, 96^3 B=2 32->32 forward, one wave per SIMD).  hipcc emitted each group's
-// halo staging (the deferred norm's VALU work and its ds_writes), the next group's fragment reads and the previous
-// brick's epilogue as blocks BETWEEN the groups' MFMA runs, and an MFMA run at one wave per SIMD leaves only 8 of
-// every 16 cycles to other instructions -- when those come as a block, the matrix pipe idles for the whole block.  v6
-// cuts every group into 8 chunks of 3 MFMAs separated by sched_barrier(0), each chunk carrying a fixed share of the
-// rest: one of the next group's 6 fragment reads, a row of the next brick's halo loads (groups 0-1), one 2-channel
-// pair of a staged row's deferred norm (groups SG0..8, row written to LDS with its fourth pair) or one row of the
-// previous brick's epilogue (group 0).  The steady state has no branches: NORM is a template parameter, out-of-volume
-// rows are zeroed by a mask instead of a branch, the 40 threads without a halo column write a dummy LDS slot, the
-// last brick re-stages itself, and the first brick's group-0 epilogue writes bias-only values that the next brick's
-// epilogue (same lanes, same addresses) overwrites.
-// INP (data gradient, no bias): the epilogue also sums the InstanceNorm-backward partials of its output
-// (GemmArgs::inpart; fixed per-lane order); the x of a brick's output voxels is loaded in its group 4, its partial
-// sums are formed in the next brick's group 1.
-// F8 (forward only; mixed bf16/fp8 of config c5): the halo is staged as OCP e4m3 (the first 8 bytes of each 16-B
-// quad, read by ds_read_b64), the weights come as e4m3 w * s[co] (mmseg_pack_conv3_fp8) and the MFMA is
-// v_mfma_f32_16x16x32_fp8_fp8 with fp32 accumulation; the epilogue multiplies by g.wdq[co] = 1 / s[co].
-template <bool NORM, int SG0 = 3, bool INP = false, bool F8 = false>
-__global__ __launch_bounds__(256, 1) void conv3_brick6_kernel(GemmArgs g, int upb, int blocks_per_nt) {
-  PROBE_BLOCK(false);
-  using T = bf16_t;
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  constexpr int BZ = 4, BY = 4, BX = 16;
-  constexpr int HZ = BZ + 2, HY = BY + 2, HX = BX + 2;
-  constexpr int RY = HX * 4, RZ = HY * RY;             // quads per halo row / plane
-  constexpr int XQ = HZ * RZ;                          // 2592 quads = 41.5 KB
-  constexpr int RN = 2;
-  constexpr int XROWS = HZ * HY;                       // 36 (z, y) halo rows
-  constexpr int XK = XROWS / 3;                        // rows per thread (3 rows per pass of 216 threads)
-  constexpr int NSG = 9 - SG0;                         // groups that write staged rows
-  constexpr int RPG = (XK + NSG - 1) / NSG;            // rows per such group
-  constexpr int PPC = RPG / 2;                         // norm pairs per chunk (4 pairs per row, 8 chunks)
-  static_assert(RPG % 2 == 0 && NSG * RPG >= XK && SG0 >= 2, "SG0: 3, 6 or 7");
-  constexpr int EPQ = 8;
-  __shared__ __attribute__((aligned(16))) float4 lds4[2 * XQ + 64];
-  T* Xl = reinterpret_cast<T*>(lds4);
-
-  const T* Bw = reinterpret_cast<const T*>(g.b);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int bz_n = g.D / BZ, by_n = g.H / BY, bx_n = g.W / BX;
-  const int nbrick = (g.M / (g.D * g.H * g.W)) * bz_n * by_n * bx_n;
-  const int blk_all = g.swz ? xcd_swizzle(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int nt = blk_all / blocks_per_nt, blk = blk_all - nt * blocks_per_nt;
-  const int n0 = nt * 32;
-  const int u_begin = blk * upb;
-  const int u_end = u_begin + upb < nbrick ? u_begin + upb : nbrick;
-  // INP: zero partials for the samples outside the block's unit range [n_lo, n_hi] (the consumer sums every
-  // block's slot of every sample; this replaces a memset of the whole partial buffer before the launch)
-  auto inp_zero = [&](int n_lo, int n_hi) {
-    if constexpr (INP) {
-      const int nsamp = g.M / (g.D * g.H * g.W);
-      if (tid < 32 && n0 + tid < g.Ncols)
-        for (int n = 0; n < nsamp; ++n)
-          if (n < n_lo || n > n_hi) {
-            float* p = g.inpart + (((long long)n * blocks_per_nt + blk) * g.Ncols + n0 + tid) * 2;
-            p[0] = 0.f;
-            p[1] = 0.f;
-          }
-    }
-  };
-  if (u_begin >= u_end || n0 >= g.Ncols) {
-    inp_zero(0, -1);
-    return;
-  }
-  const int HW = g.H * g.W;
-  const int cin = 8 << g.cpg_shift;
-  const int ldb = g.lda * (int)sizeof(T);
-  const int vox_per_n = g.D * HW;
-  const int r16 = lane & 15, kg = lane >> 4;
-
-  V8<T> wf[F8 ? 1 : 27][RN];
-  long wf8[F8 ? 27 : 1][RN];
-  if constexpr (F8) {
-    const long* B8 = reinterpret_cast<const long*>(g.b);
-#pragma unroll
-    for (int t = 0; t < 27; ++t)
-#pragma unroll
-      for (int j = 0; j < RN; ++j)
-        wf8[t][j] = B8[(long long)(t * (cin / 8) + kg) * g.Cpad + n0 + 8 * (r16 >> 2) + 4 * j + (r16 & 3)];
-#pragma unroll
-    for (int t = 0; t < 27; ++t) asm volatile("s_nop 2" : "+a"(wf8[t][0]), "+a"(wf8[t][1]));
-  } else {
-#pragma unroll
-    for (int t = 0; t < 27; ++t)
-#pragma unroll
-      for (int j = 0; j < RN; ++j)
-        wf[t][j].load(Bw + ((long long)(t * (cin / 8) + kg) * g.Cpad + n0 + 8 * (r16 >> 2) + 4 * j + (r16 & 3)) * 8);
-#pragma unroll
-    for (int t = 0; t < 27; ++t) brick4_wfence(wf[t][0].v, wf[t][1].v);
-  }
-
-  const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(g.a), 0, (int)((long long)(g.M / vox_per_n) * vox_per_n * ldb), 0x00020000);
-  const bool xact = tid < 216;
-  const int xq = tid % 72, r0 = tid / 72;
-  const int hx = xq >> 2, cg = xq & 3;
-  const int xlds0 = (hx * 4 + (cg ^ (((hx >> 2) & 1) << 1))) * EPQ;
-  // LDS destination of staged row k in buffer b: xs0 + b * xsb + k * xsk (idle threads: a dummy slot)
-  const int xs0 = xact ? xlds0 + r0 * RY * EPQ : (2 * XQ + (tid & 63)) * EPQ;
-  const int xsk = xact ? 3 * RY * EPQ : 0;
-  const int xsb = xact ? XQ * EPQ : 0;
-  struct Unit { int n, z0, y0, x0; };
-  auto unit_of = [&](int b) {
-    Unit r;
-    const int bx = b % bx_n; b /= bx_n;
-    const int by = b % by_n; b /= by_n;
-    r.z0 = (b % bz_n) * BZ;
-    r.n = b / bz_n;
-    r.y0 = by * BY;
-    r.x0 = bx * BX;
-    return r;
-  };
-  V8<T> xr[XK];
-  uint32_t rel[XK];
-#pragma unroll
-  for (int k = 0; k < XK; ++k) {
-    const int row = r0 + 3 * k, hz = row / HY, hy = row - hz * HY;
-    rel[k] = (uint32_t)((hz * HW + hy * g.W + hx) * ldb + cg * 16);
-  }
-  uint32_t xo[XK], om[XK];
-  float nmu[8], nrs[8];
-  int norm_n = -1;
-  auto set_x = [&](const Unit& q) {
-    if constexpr (NORM) {
-      if (q.n != norm_n) {
-        norm_n = q.n;
-        const int cb = q.n * cin + cg * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          nmu[j] = g.nmean[cb + j];
-          nrs[j] = g.nrstd[cb + j];
-        }
-      }
-    }
-    const int xx = q.x0 - 1 + hx;
-    const bool xok = xact && (unsigned)xx < (unsigned)g.W;
-    const int ob = ((q.n * g.D + q.z0 - 1) * g.H + q.y0 - 1) * g.W + q.x0 - 1;
-    const uint32_t base = (uint32_t)(ob * ldb);
-    if (q.z0 >= 1 && q.z0 + BZ < g.D && q.y0 >= 1 && q.y0 + BY < g.H) {
-#pragma unroll
-      for (int k = 0; k < XK; ++k) xo[k] = xok ? base + rel[k] : 0x80000000u;
-    } else {
-#pragma unroll
-      for (int k = 0; k < XK; ++k) {
-        const int row = r0 + 3 * k, hz = row / HY, hy = row - hz * HY;
-        const int zz = q.z0 - 1 + hz, yy = q.y0 - 1 + hy;
-        const bool ok = xok && (unsigned)zz < (unsigned)g.D && (unsigned)yy < (unsigned)g.H;
-        xo[k] = ok ? base + rel[k] : 0x80000000u;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < XK; ++k) om[k] = xo[k] != 0x80000000u ? ~0u : 0u;
-  };
-  auto load_row = [&](int k) { buf_load_v8<T>(xr[k], arsrc, xo[k]); };
-  // deferred norm of channels 2p, 2p+1 of staged row k: in_relu_apply's operations; out-of-volume rows stay 0
-  u32x4 sv[RPG];
-  auto norm_pair = [&](int k, int p, u32x4& o) {
-    float ha = (xr[k].get(2 * p) - nmu[2 * p]) * nrs[2 * p];
-    float hb = (xr[k].get(2 * p + 1) - nmu[2 * p + 1]) * nrs[2 * p + 1];
-    ha = ha > 0.f ? ha : 0.f;
-    hb = hb > 0.f ? hb : 0.f;
-    if constexpr (F8) {   // pairs 0, 1 -> dword 0 (low, high word), 2, 3 -> dword 1
-      if (p & 1) o[p >> 1] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(ha, hb, (int)o[p >> 1], true) & om[k];
-      else o[p >> 1] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(ha, hb, 0, false);
-    } else {
-      const bf16x2 h2 = {(__bf16)ha, (__bf16)hb};
-      o[p] = __builtin_bit_cast(uint32_t, h2) & om[k];
-    }
-  };
-  auto to_f8 = [&](int k, u32x4& o) {   // raw staged row (no norm) -> e4m3 (out-of-volume lanes read 0 -> 0)
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(xr[k].get(4 * d), xr[k].get(4 * d + 1), 0, false);
-      o[d] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(xr[k].get(4 * d + 2), xr[k].get(4 * d + 3), lo, true);
-    }
-  };
-  auto store_row = [&](int buf, int k, const u32x4& o) {
-    if constexpr (F8) {
-      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-      *reinterpret_cast<u32x2*>(Xl + buf * xsb + xs0 + k * xsk) = (u32x2){o[0], o[1]};
-    } else {
-      *reinterpret_cast<u32x4*>(Xl + buf * xsb + xs0 + k * xsk) = o;
-    }
-  };
-  auto stage_row = [&](int buf, int k) {   // whole row (prologue)
-    u32x4 o;
-    if constexpr (NORM) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p) norm_pair(k, p, o);
-    } else if constexpr (F8) {
-      to_f8(k, o);
-    } else {
-      o = __builtin_bit_cast(u32x4, xr[k].v);
-    }
-    store_row(buf, k, o);
-  };
-  int ao[3];
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) {
-    const int h = r16 + kx;
-    ao[kx] = wave * RZ + h * 4 + (kg ^ (((h >> 2) & 1) << 1));
-  }
-  float bv[RN][4], dq[F8 ? RN : 1][4];
-#pragma unroll
-  for (int j = 0; j < RN; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      bv[j][r] = g.bias ? g.bias[n0 + 8 * kg + 4 * j + r] : 0.f;
-      if constexpr (F8) dq[j][r] = g.wdq[n0 + 8 * kg + 4 * j + r];
-    }
-
-  f32x4 ev[BY][RN];
-#pragma unroll
-  for (int i = 0; i < BY; ++i)
-#pragma unroll
-    for (int j = 0; j < RN; ++j) ev[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  // row i of a finished brick: lane holds channels n0 + 8 kg + 4 j + (0..3) of voxel (z0 + wave, y0 + i, x0 + r16)
-  bf16x8 eo[BY];   // the stored rows (INP: their partial sums follow one group later)
-  auto epi_row = [&](const Unit& q, int i) {
-    const long long obase = (long long)q.n * vox_per_n;
-    const int z = q.z0 + wave, y = q.y0 + i, x = q.x0 + r16;
-    T* dst = out_at<T>(g, obase + (long long)(z * g.H + y) * g.W + x, n0 + 8 * kg);
-#pragma unroll
-    for (int j = 0; j < RN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if constexpr (F8) eo[i][4 * j + r] = (bf16_t)fmaf(ev[i][j][r], dq[j][r], bv[j][r]);
-        else eo[i][4 * j + r] = (bf16_t)(ev[i][j][r] + bv[j][r]);
-      }
-    *reinterpret_cast<bf16x8*>(dst) = eo[i];
-  };
-  // InstanceNorm-backward partials (INP): per lane the sums over its voxels of g and g (x - mean) for channels
-  // n0 + 8 kg + (0..7), g = dy if x > mean else 0 (times rstd at the flush); the first brick's epilogue runs on
-  // zeroed accumulators and x and adds 0
-  __shared__ float ired[INP ? 4 : 1][2][32];
-  float isg[8], isgx[8], imu[8];
-  int in_n = -1;
-  V8<T> xin[BY];
-  if constexpr (INP) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) isg[k] = isgx[k] = imu[k] = 0.f;
-#pragma unroll
-    for (int i = 0; i < BY; ++i) xin[i].zero();
-  }
-  auto in_flush = [&]() {
-   if constexpr (INP) {   // (the 1-wave LDS array of the plain instantiations is never read)   // block-wide, fixed order: 16-lane tree, then waves 0..3
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        isg[k] += __shfl_xor(isg[k], o, 64);
-        isgx[k] += __shfl_xor(isgx[k], o, 64);
-      }
-    if (r16 == 0)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        ired[wave][0][8 * kg + k] = isg[k];
-        ired[wave][1][8 * kg + k] = isgx[k];
-      }
-    __syncthreads();
-    if (tid < 32) {
-      const float a = ired[0][0][tid] + ired[1][0][tid] + ired[2][0][tid] + ired[3][0][tid];
-      const float c = ired[0][1][tid] + ired[1][1][tid] + ired[2][1][tid] + ired[3][1][tid];
-      float* p = g.inpart + (((long long)in_n * blocks_per_nt + blk) * g.Ncols + n0 + tid) * 2;
-      p[0] = a;
-      p[1] = c * g.inrstd[in_n * g.Ncols + n0 + tid];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) isg[k] = isgx[k] = 0.f;
-   }
-  };
-  auto in_begin = [&](const Unit& q) {   // block-uniform: the sample of the epilogue's brick
-    if constexpr (INP) {
-      if (q.n != in_n) {
-        if (in_n >= 0) in_flush();
-        in_n = q.n;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) imu[k] = g.inmean[in_n * g.Ncols + n0 + 8 * kg + k];
-      }
-    }
-  };
-  auto in_load_row = [&](const Unit& q, int i) {   // x of the lane's output voxel of row i
-    const T* X = reinterpret_cast<const T*>(g.inx) + (long long)q.n * vox_per_n * g.ldinx + n0 + 8 * kg;
-    xin[i].load(X + (long long)((q.z0 + wave) * g.H + q.y0 + i) * g.W * g.ldinx + (long long)(q.x0 + r16) * g.ldinx);
-  };
-  auto epi_inp = [&](int i, int half) {
-#pragma unroll
-    for (int k = 4 * half; k < 4 * half + 4; ++k) {
-      const float d = xin[i].get(k) - imu[k];
-      const float gg = d > 0.f ? (float)eo[i][k] : 0.f;
-      isg[k] += gg;
-      isgx[k] = fmaf(gg, d, isgx[k]);
-    }
-  };
-
-  Unit cur = unit_of(u_begin), prev = cur;
-  set_x(cur);
-#pragma unroll
-  for (int k = 0; k < XK; ++k) load_row(k);
-#pragma unroll
-  for (int k = 0; k < XK; ++k) stage_row(0, k);
-  __syncthreads();
-  int b = 0;
-  for (int u = u_begin; u < u_end; ++u) {
-    f32x4 acc[BY][RN];   // (first written by the C = 0 MFMAs of group 0)
-    Unit nxt = cur;
-    if (u + 1 < u_end) {   // (the last brick re-stages itself into the idle buffer)
-      nxt.x0 += BX;
-      if (nxt.x0 == g.W) {
-        nxt.x0 = 0;
-        nxt.y0 += BY;
-        if (nxt.y0 == g.H) {
-          nxt.y0 = 0;
-          nxt.z0 += BZ;
-          if (nxt.z0 == g.D) {
-            nxt.z0 = 0;
-            ++nxt.n;
-          }
-        }
-      }
-    }
-    set_x(nxt);
-    in_begin(prev);
-    const T* Xb = Xl + b * XQ * EPQ;
-    V8<T> af[F8 ? 1 : 2][HY];
-    long af8[F8 ? 2 : 1][HY];
-#pragma unroll
-    for (int h = 0; h < HY; ++h) {
-      if constexpr (F8) af8[0][h] = *reinterpret_cast<const long*>(Xb + (ao[0] + h * RY) * EPQ);
-      else af[0][h].load(Xb + (ao[0] + h * RY) * EPQ);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-      const int kz = q / 3, kx = q - kz * 3;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        if (q + 1 < 9 && c < HY) {     // fragment c of the next group
-          const int qn = q + 1, kzn = qn / 3, kxn = qn - kzn * 3;
-          if constexpr (F8) af8[qn & 1][c] = *reinterpret_cast<const long*>(Xb + (ao[kxn] + kzn * RZ + c * RY) * EPQ);
-          else af[qn & 1][c].load(Xb + (ao[kxn] + kzn * RZ + c * RY) * EPQ);
-        }
-        if (q == 0) {
-          load_row(c);                  // next brick's halo rows 0..7
-          if ((c & 1) == 0) epi_row(prev, c >> 1);
-        }
-        if (q == 1 && c < XK - 8) load_row(8 + c);
-        if constexpr (INP) {
-          if (q == 1) epi_inp(c >> 1, c & 1);
-          if (q == 4 && c < BY) in_load_row(cur, c);
-        }
-        if (q >= SG0) {
-#pragma unroll
-          for (int pp = 0; pp < PPC; ++pp) {
-            const int pi = c * PPC + pp;            // pair index inside the group: row slot pi / 4, pair pi % 4
-            const int k = (q - SG0) * RPG + pi / 4;
-            if (k < XK) {
-              if constexpr (NORM) norm_pair(k, pi % 4, sv[pi / 4]);
-              else if constexpr (F8) { if (pi % 4 == 0) to_f8(k, sv[pi / 4]); }
-              else if (pi % 4 == 0) sv[pi / 4] = __builtin_bit_cast(u32x4, xr[k].v);
-              if (pi % 4 == 3) store_row(b ^ 1, k, sv[pi / 4]);
-            }
-          }
-        }
-#pragma unroll
-        for (int m = 3 * c; m < 3 * c + 3; ++m) {
-          const int ky = m >> 3, i = (m >> 1) & 3, j = m & 1;
-          if constexpr (F8) {
-            if (q == 0 && ky == 0) mfma_aw80(acc[i][j], wf8[kx][j], af8[0][i]);
-            else mfma_aw8(acc[i][j], wf8[kz * 9 + ky * 3 + kx][j], af8[q & 1][i + ky]);
-          } else {
-            if (q == 0 && ky == 0) mfma_aw0(acc[i][j], wf[kx][j].v, af[0][i].v);
-            else mfma_aw(acc[i][j], wf[kz * 9 + ky * 3 + kx][j].v, af[q & 1][i + ky].v);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // one MFMA-result hazard fence over all 8 accumulators before they are copied
-    asm volatile("s_nop 7\n\ts_nop 7" : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[1][0]), "+a"(acc[1][1]),
-                 "+a"(acc[2][0]), "+a"(acc[2][1]), "+a"(acc[3][0]), "+a"(acc[3][1]));
-#pragma unroll
-    for (int i = 0; i < BY; ++i)
-#pragma unroll
-      for (int j = 0; j < RN; ++j) ev[i][j] = acc[i][j];
-    prev = cur;
-    __syncthreads();   // buffer b^1 is complete; buffer b is free for the brick after next
-    b ^= 1;
-    cur = nxt;
-  }
-  in_begin(prev);
-#pragma unroll
-  for (int i = 0; i < BY; ++i) {
-    epi_row(prev, i);
-    if constexpr (INP) {
-      epi_inp(i, 0);
-      epi_inp(i, 1);
-    }
-  }
-  if constexpr (INP) {
-    in_flush();
-    inp_zero(u_begin / (nbrick / (g.M / vox_per_n)), in_n);
-  }
-  PROBE_BLOCK(true);
-}
 
 // ------------------------------------- runtime-brick conv (small volumes)
 // conv3_brick2_kernel for volumes whose sides are not multiples of 8 (the
@@ -2035,29 +1441,6 @@ __global__ __launch_bounds__(256 * KW, (sizeof(T) == 2 && KW == 1) ? 2 : 1) void
 // ---- the kernel choice of a forward / data-gradient GEMM launch.  choose_gemm is the only place that decides it:
 // launch_gemm launches what it returns, and the planning queries (mmseg_conv3_splits, _group_ok, _norm_ok,
 // _fp8_ok, _dgrad_in_chunks, mmseg_conv3_kernel) answer from it without a GPU.
-enum GemmKernel {
-  GK_BRICKR,   // conv3_brickr_kernel: runtime brick (small volumes, grouped launches), splits over 32-channel chunks
-  GK_BRICK8,   // conv3_brick8_kernel: 8-wave 8x8x8 brick, LDS-DMA staging
-  GK_BRICK2_BN48, GK_BRICK2,   // conv3_brick2_kernel: 4x8x8 brick, 48-column tiles; 64 / 32-column tiles
-  GK_BRICK6,   // conv3_brick6_kernel: W % 16, one input chunk, 32 columns (deferred norm, e4m3, IN-backward partials)
-  GK_BRICK4,   // conv3_brick4_kernel: one input chunk, 32 columns, persistent
-  GK_BRICK3,   // conv3_brick3_kernel: 32-column tiles, persistent
-  GK_BRICK1,   // conv3_brick_kernel: the first brick generation (MMSEG_BRICK=1)
-  GK_GEMM_64x256, GK_GEMM_64x192, GK_GEMM_64x128, GK_GEMM_128x48, GK_GEMM_128x96, GK_GEMM_128x32, GK_GEMM_128x64
-};
-struct GemmChoice {
-  int kernel;          // GemmKernel
-  const char* name;    // the family noted for mmseg_last_kernel() / the per-kernel timer
-  int bn;              // column tile
-  int grid, block;
-  int upb, bpn;        // persistent kernels (brick6 / brick4 / brick3): units per block, blocks per column tile
-  int bz, by, bx;      // GK_BRICKR: the brick
-  bool b32, kw2;       // 32-bit offset halo staging; GK_BRICKR: two waves per SIMD over an in-block chunk split
-  int ksplit;          // the launch's split count (GK_BRICKR: clamped to whole chunk ranges)
-  bool reduce;         // a split-K reduce follows
-  int ks_want;         // CONV3: the split count this shape wants (mmseg_conv3_splits)
-};
-
 // tsize: element bytes.  A grouped launch (g.grp_n > 0) takes the runtime-brick kernel even where the (4, 8, 8)-brick
 // family fits: only it reads per-group weights (24^3 with MMSEG_GROUP_FORCE_R).  A deferred norm, IN-backward
 // partials or e4m3 weights (g.nmean / g.inpart / g.wdq) are served by brick6 alone; the caller checks it got it.
@@ -2295,22 +1678,6 @@ inline bool tile_in_pitch(const GemmArgs& g, int BN) { return (long long)((g.Nco
                   (const char*)(NAME), (int)(BN), (G).Ncols, (G).Cpad);                                          \
     mmseg::note_kernel(NAME);                                                                                    \
   } while (0)
-
-// The W % 16 one-chunk 32-column conv: brick6 (forward, deferred-norm forward, e4m3 forward, and the data gradient
-// with the InstanceNorm-backward partials), on the grid choose_gemm gave it.
-void launch_brick6(const GemmArgs& g, const GemmChoice& c, hipStream_t s) {
-  const dim3 grid(c.grid), block(c.block);
-  if (g.wdq) {   // e4m3 forward (mmseg_conv3_fwd_fp8)
-    if (g.nmean) MMSEG_LAUNCH((conv3_brick6_kernel<true, 6, false, true>), grid, block, 0, s, g, c.upb, c.bpn);
-    else MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, false, true>), grid, block, 0, s, g, c.upb, c.bpn);
-  } else if (g.inpart) {   // mmseg_conv3_dgrad_in (no bias); the kernel zeroes the partials of samples a block does not touch
-    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6, true>), grid, block, 0, s, g, c.upb, c.bpn);
-  } else if (g.nmean) {
-    MMSEG_LAUNCH((conv3_brick6_kernel<true, 6>), grid, block, 0, s, g, c.upb, c.bpn);
-  } else {
-    MMSEG_LAUNCH((conv3_brick6_kernel<false, 6>), grid, block, 0, s, g, c.upb, c.bpn);
-  }
-}
 
 // 4 consecutive columns per thread in gemm_splitk_reduce (for the transposed conv: 4 channels of one child voxel,
 // Cout % 4 == 0)
@@ -3309,199 +2676,6 @@ __global__ __launch_bounds__(512, (MT == 2 && V == 2) ? 2 : 1) void wgrad_brick2
 // ReLU is applied in place to the landed halo (each thread its fixed channel group), one extra barrier.
 // (WD_OOB, wd_rsrc, wd_dma16: mmseg_common.h)
 
-// ------------------------------------------------- brick conv v8 (3^3, bf16, 8 waves, LDS-DMA staging)
-// conv3_brick2's BN-column tile with the block grown to an (8 ZP) x 8 x 8 brick: 8 waves, wave w owns z planes
-// w ZP .. w ZP + ZP - 1 (64 voxels each = 4 row tiles of two 8-voxel x rows) x BN columns (BN 64 with ZP 1; BN 32
-// with ZP 2, so a wave still runs 16 MFMAs per tap).  Both operands are staged by LDS-DMA
-// (buffer_load ... lds): no staging registers and no ds_write pass, which in conv3_brick2 were ~2 VALU + 0.7 SALU
-// per MFMA around a per-stage register round trip of the weights.  Per block:
-//   * the halo image of one 32-channel input chunk: 10 x 10 rows of 10 voxels x 4 quads + 2 pad quads (the pad
-//     keeps the 16-lane groups of the A-fragment ds_read_b128 on distinct banks), single buffer, re-filled
-//     between chunks (that refill is the one exposed load: 1 of 3 * nchunk stages);
-//   * the weight slice of one (chunk, kz) stage: 9 taps x BN columns x 32 channels in the B-operand order
-//     [tap][col][4 quads, channel group kg at slot kg ^ w2_swz(col)], double buffered: stage s + 1's slice
-//     lands while stage s is multiplied.
-// The lane-linear DMA destination is matched by computing, per lane, the source of the quad that belongs at its
-// LDS slot (pads and out-of-volume voxels read zeros through the OOB offset).  Each staged weight slice feeds
-// 8 waves x 9 taps x 4 ZP x RN MFMAs (twice conv3_brick2's).  LDS 141 KB (BN 64) / 155 KB (BN 32): one block per
-// CU, two waves per SIMD.  Requirements (host): bf16, Cin % 32 == 0, Ncols % BN == 0, D % 8 ZP, H % 8, W % 8, ksplit == 1, no
-// deferred norm / IN partials, the A and B extents < 2^31 bytes.
-template <int BN, int ZP>
-__global__ __launch_bounds__(512, 1) void conv3_brick8_kernel(GemmArgs g) {
-  PROBE_BLOCK(false);
-  PROBE_DECL();
-  typedef bf16_t T;
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  constexpr int QV = 4;                                  // 16-B quads per halo voxel (32 channels)
-  constexpr int BZ = 8 * ZP;                            // z planes per brick (ZP per wave)
-  constexpr int HXY = 10, HZ = BZ + 2;
-  constexpr int RY = HXY * QV + 2, RZ = HXY * RY;        // 42 quads per halo row, 420 per plane
-  constexpr int XQ = HZ * RZ;                            // 4200 (ZP 1) / 7560 (ZP 2)
-  constexpr int XI = (XQ + 63) / 64, XK = (XI + 7) / 8;  // 66 / 119 wave-instructions
-  constexpr int XQP = XI * 64;
-  constexpr int WQ = 9 * BN * QV;                        // 2304 quads (BN 64)
-  constexpr int WI = WQ / 64, WK = (WI + 7) / 8;         // 36, <= 5 per wave
-  constexpr int RM = 4 * ZP, RN = BN / 16;
-  constexpr int EPQ = 8;                                 // bf16 per quad
-  static_assert(WQ % 64 == 0, "weight slice must be whole wave-instructions");
-  __shared__ __attribute__((aligned(16))) float4 lds4[XQP + 2 * WQ];
-  T* Xl = reinterpret_cast<T*>(lds4);
-  T* Wl = reinterpret_cast<T*>(lds4 + XQP);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int bz_n = g.D / BZ, by_n = g.H >> 3, bx_n = g.W >> 3;
-  const int nbrick = (g.M / (g.D * g.H * g.W)) * bz_n * by_n * bx_n;
-  const int nt_n = g.Ncols / BN;
-  const int tile = g.swz ? xcd_swizzle(blockIdx.x, nbrick * nt_n) : (int)blockIdx.x;
-  int bidx = tile % nbrick;
-  const int nt = tile / nbrick;
-  const int bx = bidx % bx_n; bidx /= bx_n;
-  const int by = bidx % by_n; bidx /= by_n;
-  const int bz = bidx % bz_n;
-  const int n = bidx / bz_n;
-  const int z0 = bz * BZ, y0 = by * 8, x0 = bx * 8;
-  const int n0 = nt * BN;
-  const int cin = 8 << g.cpg_shift;
-  const int nchunk = gemm_nchunk(g);
-  const int nstage = nchunk * 3;
-  const long long HW = (long long)g.H * g.W;
-  const long long nbase = (long long)n * g.D * HW;
-
-  const wd_rsrc_t arsrc = wd_rsrc(g.a, (uint32_t)((long long)g.M * g.lda * 2));
-  const int KGp = (g.KG + 3) & ~3;
-  const wd_rsrc_t brsrc = wd_rsrc(g.b, (uint32_t)((long long)KGp * g.Cpad * 16));
-
-  // per-lane halo sources: quad p = 64 m + lane of instruction m = wave + 8 kk, byte offset of chunk 0 or OOB
-  uint32_t xo[XK];
-#pragma unroll
-  for (int kk = 0; kk < XK; ++kk) {
-    const int p = (wave + 8 * kk) * 64 + lane;
-    const int row = p / RY, qi = p - row * RY;
-    const int hz = row / HXY, hy = row - hz * HXY, hx = qi >> 2, cg = qi & 3;
-    const int z = z0 - 1 + hz, y = y0 - 1 + hy, x = x0 - 1 + hx;
-    const bool ok = p < XQ && qi < HXY * QV && (unsigned)z < (unsigned)g.D && (unsigned)y < (unsigned)g.H &&
-                    (unsigned)x < (unsigned)g.W;
-    xo[kk] = ok ? (uint32_t)((((n * g.D + z) * g.H + y) * g.W + x) * g.lda * 2 + cg * 16) : WD_OOB;
-  }
-  // per-lane weight sources: quad p = (t9 * BN + col) * 4 + slot, channel group slot ^ w2_swz(col)
-  uint32_t wo[WK];
-#pragma unroll
-  for (int kk = 0; kk < WK; ++kk) {
-    const int p = (wave + 8 * kk) * 64 + lane;
-    const int q = p >> 2, col = q % BN, t9 = q / BN;
-    const int cg = (p & 3) ^ w2_swz(col);
-    wo[kk] = (uint32_t)(((t9 * (cin / 8) + cg) * g.Cpad + n0 + col) * 16);
-  }
-  const uint32_t xl_base = (uint32_t)(uintptr_t)(lds_ptr_t)Xl;
-  const uint32_t wl_base = (uint32_t)(uintptr_t)(lds_ptr_t)Wl;
-  auto issue_x = [&](int c) {
-#pragma unroll
-    for (int kk = 0; kk < XK; ++kk) {
-      const int m = wave + 8 * kk;
-      if (m < XI)
-        wd_dma16(__builtin_amdgcn_readfirstlane((int)(xl_base + m * 1024)),
-                 xo[kk] == WD_OOB ? WD_OOB : xo[kk] + c * 64, arsrc);
-    }
-  };
-  auto issue_w = [&](int s, int buf) {
-    const int c = s / 3, kz = s - c * 3;
-    const uint32_t so = (uint32_t)((kz * 9 * (cin / 8) + c * 4) * g.Cpad * 16);
-#pragma unroll
-    for (int kk = 0; kk < WK; ++kk) {
-      const int m = wave + 8 * kk;
-      if (m < WI)
-        wd_dma16(__builtin_amdgcn_readfirstlane((int)(wl_base + (buf * WQ + m * 64) * 16)), wo[kk] + so, brsrc);
-    }
-  };
-
-  f32x4 acc[RM][RN];
-#pragma unroll
-  for (int i = 0; i < RM; ++i)
-#pragma unroll
-    for (int j = 0; j < RN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int r16 = lane & 15, kg = lane >> 4;
-  int aq[RM];   // halo quad of the lane's row for tap (0,0,0), group kg: z plane wave * ZP + i / 4
-#pragma unroll
-  for (int i = 0; i < RM; ++i)
-    aq[i] = (wave * ZP + (i >> 2)) * RZ + (2 * (i & 3) + (r16 >> 3)) * RY + (r16 & 7) * QV + kg;
-  int bq[RN];
-#pragma unroll
-  for (int j = 0; j < RN; ++j) {
-    const int col = j * 16 + r16;
-    bq[j] = col * QV + (kg ^ w2_swz(col));
-  }
-
-  PROBE_T();
-  issue_x(0);
-  issue_w(0, 0);
-  __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces have landed
-  __syncthreads();
-  PROBE_T();
-  for (int s = 0; s < nstage; ++s) {
-    const int kz = s % 3, b = s & 1;
-    const bool more = s + 1 < nstage;
-    if (more) issue_w(s + 1, b ^ 1);
-    const T* Wb = Wl + b * WQ * EPQ;
-    V8<T> af[2][RM], bf[2][RN];
-    auto rd = [&](int t9, int k) {
-      const int ky = t9 / 3, kx = t9 - ky * 3;
-      const int hoff = kz * RZ + ky * RY + kx * QV;
-#pragma unroll
-      for (int j = 0; j < RN; ++j) bf[k][j].load(Wb + (t9 * BN * QV + bq[j]) * EPQ);
-#pragma unroll
-      for (int i = 0; i < RM; ++i) af[k][i].load(Xl + (aq[i] + hoff) * EPQ);
-    };
-    rd(0, 0);
-#pragma unroll
-    for (int t9 = 0; t9 < 9; ++t9) {
-      if (t9 < 8) rd(t9 + 1, (t9 + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < RM; ++i)
-#pragma unroll
-        for (int j = 0; j < RN; ++j) mfma_step<T>(acc[i][j], af[t9 & 1][i], bf[t9 & 1][j]);
-    }
-    if (more) {
-      if ((s + 1) % 3 == 0) {           // next chunk: every wave is done with this halo, then refill it
-        __syncthreads();
-        issue_x((s + 1) / 3);
-      }
-      PROBE_T();
-      __builtin_amdgcn_s_waitcnt(0x0f70);
-      __syncthreads();
-    }
-    PROBE_T();
-  }
-
-  // epilogue: acc (+bias) -> LDS tile [512 ZP voxels][BN + 8] -> 16-B stores
-  __syncthreads();
-  T* El = reinterpret_cast<T*>(lds4);
-  constexpr int EP = BN + 8;
-  static_assert(512 * ZP * EP * 2 <= (XQP + 2 * WQ) * 16, "epilogue tile must fit");
-#pragma unroll
-  for (int j = 0; j < RN; ++j) {
-    const int col = j * 16 + r16;
-    const float bv = (g.bias && n0 + col < g.Ncols) ? g.bias[n0 + col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < RM; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        El[((wave * ZP + (i >> 2)) * 64 + 16 * (i & 3) + 4 * kg + r) * EP + col] = from_f<T>(acc[i][j][r] + bv);
-  }
-  __syncthreads();
-  constexpr int CG = BN / 8;
-#pragma unroll
-  for (int k = 0; k < ZP * CG; ++k) {
-    const int e = tid + k * 512;
-    const int v = e / CG, cg = e % CG;
-    const int z = z0 + (v >> 6), y = y0 + ((v >> 3) & 7), x = x0 + (v & 7);
-    V8<T> o;
-    o.load(El + v * EP + cg * 8);
-    o.store(out_at<T>(g, nbase + z * HW + (long long)y * g.W + x, n0 + cg * 8));
-  }
-  PROBE_T();
-  PROBE_BLOCK(true);
-}
 // PIPE: the fragment reads of the next (dy plane, tap) step are issued before the current step's MFMAs
 // MTC < MT: only the first MTC 16-row tiles are multiplied (the rest are output-channel padding, WgradArgs::pad16);
 // staging and the epilogue keep the MT-row layout, the skipped rows' accumulators stay zero
@@ -4377,177 +3551,6 @@ WBrick plan_wgrad_brickr(int D, int H, int W) {
   return brows >= 32 ? best : WBrick{0, 0, 0};
 }
 
-// part[ks][row][col] -> torch-layout gradient (fixed-order sum over ks).
-//   CONV3 : grad[co][ci][tap]    row=co, col = tap*Cin_pad + ci, ci < Cin_real
-//   POINT : grad[co][ci]         row=co, col = ci
-//   CONVT : grad[ci][co][tap]    row=ci, col = tap*Cout + co
-struct WReduceArgs {
-  const float* part;
-  float* grad;
-  const float* bias_part;
-  float* bias_grad;
-  int Ca, Ncols, ksplit;
-  int cpad, creal;    // per-tap channel count in cols (padded) and real count
-  int ntap;           // 27 (CONV3), 1 (POINT), 8 (CONVT)
-  int accumulate;
-  int chmajor;        // cols are channel-major (col = c*ntap + tap, brick2/brickr partials) instead of tap-major
-  int frag_mt;        // > 0: wgrad_dma's fragment-native partials (MT 16-row tiles per block), see wgrad_dma_kernel
-  int nchunk;         // frag_mt > 0: 32-channel chunks per tile row
-  // grouped (blockIdx.y = group gi < gridDim.y): splits [gi * ksplit, (gi + 1) * ksplit) of the partials (ksplit
-  // counts one group's splits), written to grad + gi * grad_gstride / bias_grad + gi * bias_gstride
-  long long grad_gstride;
-  int bias_gstride;
-  int vec4;           // host-set (wred_vec4): channel-major sums as 16-B stores
-};
-
-// 256 threads = (256/S) float4 columns x S split slices: slice s sums splits
-// k = s, s+S, ... with 16-B loads, then the S slice sums are added in slice
-// order -> deterministic.  S follows ksplit (1 for a few splits, up to 64 for
-// thousands), so every thread has a few independent loads in flight.  Bias
-// partials ([ks][Ca], after the weight columns) are summed by the blocks past
-// the weight range.
-template <int U>
-__device__ __forceinline__ void wred_body(WReduceArgs g, const int S, const int bx, const int gy, float4* red) {
-  if (gy) {                                   // grouped: this group's splits and gradient
-    const long long gi = gy;
-    g.part += gi * g.ksplit * ((long long)g.Ca * g.Ncols);
-    if (g.bias_part) g.bias_part += gi * g.ksplit * g.Ca;
-    g.grad += gi * g.grad_gstride;
-    if (g.bias_grad) g.bias_grad += gi * g.bias_gstride;
-  }
-  const int NC = 256 / S;                     // float4 columns per block
-  const int col4 = threadIdx.x % NC, sl = threadIdx.x / NC;
-  const long long total = (long long)g.Ca * g.Ncols;   // multiple of 4
-  const long long e0 = ((long long)bx * NC + col4) * 4;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (e0 < total) {
-    const float4* p = reinterpret_cast<const float4*>(g.part + e0);
-    const long long stride4 = total / 4;
-    // U loads in flight per thread (the sum order stays k = sl, sl + S, ...)
-    for (int k0 = sl; k0 < g.ksplit; k0 += U * S) {
-      float4 a[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = k0 + u * S;
-        if (k < g.ksplit) a[u] = p[(long long)k * stride4];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (k0 + u * S < g.ksplit) {
-          v.x += a[u].x; v.y += a[u].y; v.z += a[u].z; v.w += a[u].w;
-        }
-      }
-    }
-  } else if (g.bias_part) {
-    const long long r0 = e0 - total;   // bias rows r0 .. r0+3
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (r0 + q >= g.Ca) break;
-      float a = 0.f;
-      for (int k = sl; k < g.ksplit; k += S) a += g.bias_part[(long long)k * g.Ca + r0 + q];
-      (&v.x)[q] = a;
-    }
-  }
-  if (S > 1) {
-    // slice sums: a fixed pairwise tree (S = 16..64 made the former serial sweep of one thread per column the
-    // kernel's critical path)
-    red[sl * NC + col4] = v;
-    __syncthreads();
-#pragma unroll
-    for (int h = S / 2; h > 0; h >>= 1) {
-      if (sl < h) {
-        const float4 a = red[(sl + h) * NC + col4];
-        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-        red[sl * NC + col4] = v;
-      }
-      __syncthreads();
-    }
-    if (sl != 0) return;
-  }
-  // channel-major partials: the four sums are four consecutive gradient floats (col = c ntap + tap and the torch
-  // offset (row creal + c) ntap + tap differ by row (Ncols - creal ntap), a multiple of 4, and the real-channel
-  // boundary col = creal ntap is one too) -- one 16-B store instead of four 4-B ones
-  if (g.vec4 && e0 < total && g.frag_mt == 0 && g.chmajor) {
-    const long long row = e0 / g.Ncols;
-    const long long col = e0 - row * g.Ncols;
-    if (col >= (long long)g.creal * g.ntap) return;   // channel padding: dropped
-    float4* d = reinterpret_cast<float4*>(g.grad + row * ((long long)g.creal * g.ntap) + col);
-    if (g.accumulate) {
-      const float4 o = *d;
-      v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-    }
-    *d = v;
-    return;
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const long long idx = e0 + q;
-    const float val = (&v.x)[q];
-    if (idx >= total) {
-      const long long row = idx - total;
-      if (!g.bias_part || row >= g.Ca) continue;
-      g.bias_grad[row] = g.accumulate ? g.bias_grad[row] + val : val;
-      continue;
-    }
-    int row, tt, c;
-    if (g.frag_mt > 0) {
-      // tile (rt, ct) of CO x (27 taps x 32 channels), inside it ((tap * MT + i) * 2 + j) * 256 + lane * 4 + r
-      const int CO = g.frag_mt * 16, tsz = CO * 27 * 32;
-      const int tile = (int)(idx / tsz), loc = (int)(idx - (long long)tile * tsz);
-      const int rt = tile / g.nchunk, ct = tile - rt * g.nchunk;
-      const int f = loc >> 8, e = loc & 255, lane = e >> 2, r = e & 3;
-      const int j = f & 1, i = (f >> 1) % g.frag_mt;
-      tt = (f >> 1) / g.frag_mt;
-      row = rt * CO + 16 * i + 4 * (lane >> 4) + r;
-      c = ct * 32 + 16 * j + (lane & 15);
-      if (row >= g.Ca || c >= g.creal) continue;   // past the tiles (channel padding): never written, sum dropped
-      const long long dst = ((long long)row * g.creal + c) * g.ntap + tt;
-      if (g.accumulate) g.grad[dst] += val;
-      else g.grad[dst] = val;
-      continue;
-    }
-    row = (int)(idx / g.Ncols);
-    const int col = (int)(idx - (long long)row * g.Ncols);
-    if (g.chmajor) {
-      c = col / g.ntap;
-      tt = col - c * g.ntap;
-    } else {
-      tt = col / g.cpad;
-      c = col - tt * g.cpad;
-    }
-    if (c >= g.creal || tt >= g.ntap) continue;
-    const long long dst = ((long long)row * g.creal + c) * g.ntap + tt;   // torch layout [row][c_real][tap]
-    if (g.accumulate) g.grad[dst] += val;
-    else g.grad[dst] = val;
-  }
-}
-
-template <int S, int U = 4>
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(WReduceArgs g) {
-  __shared__ float4 red[256];
-  wred_body<U>(g, S, blockIdx.x, blockIdx.y, red);
-}
-
-// Several layers' split reduces in one launch (mmseg_wgrad_reduce_flush): descriptor k owns blocks
-// [blk0[k], blk0[k + 1]) = groups x nbx[k], each summed exactly as its own wgrad_reduce_kernel<S[k]> launch would
-// (same slices, same fixed order: bitwise the same gradient).
-constexpr int WRB_MAX = 30;
-struct WReduceBatch {
-  int n;
-  int blk0[WRB_MAX + 1];
-  int nbx[WRB_MAX];
-  int S[WRB_MAX];
-  WReduceArgs d[WRB_MAX];
-};
-__global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(WReduceBatch b) {
-  __shared__ float4 red[256];
-  const int bid = blockIdx.x;
-  int k = 0;
-  while (k + 1 < b.n && bid >= b.blk0[k + 1]) ++k;
-  const int local = bid - b.blk0[k];
-  wred_body<4>(b.d[k], b.S[k], local % b.nbx[k], local / b.nbx[k], red);
-}
-
 // Column sums (bias gradient): db[c] = sum_v dy[v][c], split over voxels.
 template <typename T>
 __global__ void colsum_partial_kernel(const T* __restrict__ dy, int ld, int C, long long V, long long vps,
@@ -4600,362 +3603,6 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restr
   if (threadIdx.x == 0) {
     const float t = ((wred[0] + wred[1]) + wred[2]) + wred[3];
     out[c] = accumulate ? out[c] + t : t;
-  }
-}
-
-// ------------------------------------------------------------ weight pack
-// dst[kgi][col][j] (T), KGp x Cpad x 8, from fp32 torch-layout weights.
-//   0 CONV3_FWD  : W[Co][Ci][27]; kgi = tap*(Cip/8)+c8, col = co, ci = c8*8+j
-//   1 CONV3_DGRAD: kgi = tap*(Co/8)+c8, col = ci, co = c8*8+j, tap' = 26-tap
-//   2 POINT_FWD  : W[Co][Ci]; kgi = c8, col = co, ci = c8*8+j
-//   3 POINT_DGRAD: kgi = c8, col = ci, co = c8*8+j
-//   4 CONVT_FWD  : W[Ci][Co][8]; kgi = c8 (ci), col = tap*Co + co
-//   5 CONVT_DGRAD: kgi = tap*(Co/8)+c8, col = ci, co = c8*8+j
-//   6 / 7        : modes 1 / 5 with Cip = the padded output-channel count (rows co >= Co zero)
-struct PackArgs {
-  const float* w;
-  void* dst;
-  int Co, Ci, Cip;  // Cip: padded input channels (multiple of 8) for CONV3_FWD
-  int KG, KGp, Cpad;
-};
-
-// Value of packed element (kgi, col, j) of a mode-`mode` image (0 outside the weight).
-__device__ __forceinline__ float pack_value(const float* __restrict__ w, int mode, int Co, int Ci, int Cip, int kgi,
-                                            int col, int j) {
-  switch (mode) {
-    case 0: {
-      const int cpg = Cip >> 3, t = kgi / cpg, ci = (kgi % cpg) * 8 + j, co = col;
-      if (co < Co && ci < Ci) return w[((long long)co * Ci + ci) * 27 + t];
-    } break;
-    case 1: {
-      const int cpg = Co >> 3, t = kgi / cpg, co = (kgi % cpg) * 8 + j, ci = col;
-      if (ci < Ci) return w[((long long)co * Ci + ci) * 27 + (26 - t)];
-    } break;
-    case 2: {
-      const int ci = kgi * 8 + j, co = col;
-      if (co < Co && ci < Ci) return w[(long long)co * Ci + ci];
-    } break;
-    case 3: {
-      const int co = kgi * 8 + j, ci = col;
-      if (ci < Ci && co < Co) return w[(long long)co * Ci + ci];
-    } break;
-    case 4: {
-      const int ci = kgi * 8 + j;
-      const int t = col / Co, co = col % Co;
-      if (t < 8 && ci < Ci) return w[((long long)ci * Co + co) * 8 + t];
-    } break;
-    case 5: {
-      const int cpg = Co >> 3, t = kgi / cpg, co = (kgi % cpg) * 8 + j, ci = col;
-      if (ci < Ci) return w[((long long)ci * Co + co) * 8 + t];
-    } break;
-    case 6: {   // CONV3_DGRAD over Cop = Cip padded output channels (zero rows co >= Co)
-      const int cpg = Cip >> 3, t = kgi / cpg, co = (kgi % cpg) * 8 + j, ci = col;
-      if (ci < Ci && co < Co) return w[((long long)co * Ci + ci) * 27 + (26 - t)];
-    } break;
-    case 7: {   // CONVT_DGRAD over Cop = Cip padded output channels
-      const int cpg = Cip >> 3, t = kgi / cpg, co = (kgi % cpg) * 8 + j, ci = col;
-      if (ci < Ci && co < Co) return w[((long long)ci * Co + co) * 8 + t];
-    } break;
-  }
-  return 0.f;
-}
-
-template <typename T>
-__global__ void pack_weight_kernel(PackArgs g, int mode) {
-  long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long total = (long long)g.KGp * g.Cpad * 8;
-  if (idx >= total) return;
-  const int j = (int)(idx & 7);
-  const long long q = idx >> 3;
-  const int col = (int)(q % g.Cpad);
-  const int kgi = (int)(q / g.Cpad);
-  const float v = kgi < g.KG ? pack_value(g.w, mode, g.Co, g.Ci, g.Cip, kgi, col, j) : 0.f;
-  reinterpret_cast<T*>(g.dst)[idx] = from_f<T>(v);
-}
-
-// Batched 3^3 pack: one launch writes BOTH operand images of every 3^3 conv of
-// a model (forward [27*Cip/8][Cpad][8] and flipped/transposed data-gradient
-// [27*Co/8][Cpad_d][8]) from ONE coalesced read of the fp32 master weights.
-// Block = (8 output channels, 32 input channels) of one layer: the 8 x 32 x 27
-// source floats are contiguous runs per output channel, staged in LDS, then
-// written as 16-B vectors (8 input channels for the forward image, 8 output
-// channels for the data-gradient image).  Entries the block does not own
-// (K padding, Cin padding of the stem) are zero from allocation.
-struct Pack3Desc {
-  const float* w;       // [Co][Ci][27]
-  void* wf;             // forward image
-  void* wd;             // data-gradient image or null
-  int Co, Ci, Cip, Cpad, Cpad_d;
-  int block_begin;      // first block of this layer in the launch
-  int Cop;              // data-gradient reduction channels (pack mode 6: padded Co; 0 = Co)
-  int pad1;
-};
-
-// The two operand images of one (8 co x 32 ci) tile of a 3^3 conv's weight staged in sw[co][ci][tap] (ci >= cis
-// zero): forward image (tap, 8-ci group, co) and data-gradient image (tap s -> kgi = (26 - s) * Cop/8 + co0/8,
-// column ci, 8 co per vector; rows co >= Co of a padded image are zero from allocation), 16-B stores.
-template <typename T>
-__device__ __forceinline__ void pack3_write(const float (*sw)[33][29], void* wfp, void* wdp, int Co, int Cip, int Cpad,
-                                            int Cpad_d, int Cop, int co0, int ci0, int cis) {
-  const int tid = threadIdx.x;
-  const int cpg = Cip >> 3;
-  const int ngrp = ((Cip - ci0) < 32 ? (Cip - ci0) : 32) >> 3;
-  T* wf = reinterpret_cast<T*>(wfp);
-  for (int e = tid; e < 27 * 4 * 8; e += 256) {
-    const int co = e & 7, cg = (e >> 3) & 3, t = e >> 5;
-    if (cg >= ngrp || co0 + co >= Co) continue;
-    V8<T> v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v.set(j, sw[co][cg * 8 + j][t]);
-    const long long kgi = (long long)t * cpg + (ci0 >> 3) + cg;
-    v.store(wf + (kgi * Cpad + co0 + co) * 8);
-  }
-  if (wdp == nullptr) return;
-  const int cpgd = (Cop > 0 ? Cop : Co) >> 3;
-  T* wd = reinterpret_cast<T*>(wdp);
-  for (int e = tid; e < 27 * 32; e += 256) {
-    const int ci = e & 31, t = e >> 5;
-    if (ci >= cis) continue;
-    V8<T> v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v.set(j, sw[j][ci][t]);
-    const long long kgi = (long long)(26 - t) * cpgd + (co0 >> 3);
-    v.store(wd + (kgi * Cpad_d + ci0 + ci) * 8);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void pack_conv3_batched_kernel(const Pack3Desc* __restrict__ descs, int n) {
-  __shared__ float sw[8][33][29];   // padded: conflict-free image reads (the [8][32][28] form was 32-way on the forward image)
-  int lo = 0, hi = n - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (descs[mid].block_begin <= b) lo = mid;
-    else hi = mid - 1;
-  }
-  const Pack3Desc d = descs[lo];
-  const int nci = (d.Ci + 31) / 32;
-  const int lb = b - d.block_begin;
-  const int co0 = (lb / nci) * 8, ci0 = (lb % nci) * 32;
-  const int cis = d.Ci - ci0 < 32 ? d.Ci - ci0 : 32;
-  const int tid = threadIdx.x;
-  if (cis == 32 && co0 + 8 <= d.Co && (d.Ci & 3) == 0) {
-    // full tile: each co row of the tile is 864 contiguous floats, 16-B aligned -> float4 loads
-    for (int e = tid; e < 8 * 216; e += 256) {
-      const int co = e / 216, r4 = (e - co * 216) * 4;
-      const float4 v = *reinterpret_cast<const float4*>(d.w + ((long long)(co0 + co) * d.Ci + ci0) * 27 + r4);
-      const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int r = r4 + k, ci = r / 27, t = r - ci * 27;
-        sw[co][ci][t] = vv[k];
-      }
-    }
-  } else {
-    for (int e = tid; e < 8 * 32 * 27; e += 256) {
-      const int co = e / (32 * 27), r = e - co * (32 * 27);
-      const int ci = r / 27, t = r - ci * 27;
-      sw[co][ci][t] = (ci < cis && co0 + co < d.Co) ? d.w[((long long)(co0 + co) * d.Ci + ci0) * 27 + r] : 0.f;
-    }
-  }
-  __syncthreads();
-  pack3_write<T>(sw, d.wf, d.wd, d.Co, d.Cip, d.Cpad, d.Cpad_d, d.Cop, co0, ci0, cis);
-}
-
-// Batched pack: one launch packs every layer of a model (descriptor table in device memory).
-struct PackDesc {
-  const float* w;
-  void* dst;
-  int mode, Co, Ci, Cip, KG, KGp, Cpad, pad0;
-  long long begin;   // first element (of the virtual concatenation) owned by this descriptor
-};
-
-template <typename T>
-__global__ void pack_weight_batched_kernel(const PackDesc* __restrict__ descs, int n, long long total) {
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long long)gridDim.x * blockDim.x) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {                    // last descriptor with begin <= idx
-      const int mid = (lo + hi + 1) >> 1;
-      if (descs[mid].begin <= idx) lo = mid;
-      else hi = mid - 1;
-    }
-    const PackDesc d = descs[lo];
-    const long long li = idx - d.begin;
-    const int j = (int)(li & 7);
-    const long long q = li >> 3;
-    const int col = (int)(q % d.Cpad);
-    const int kgi = (int)(q / d.Cpad);
-    const float v = kgi < d.KG ? pack_value(d.w, d.mode, d.Co, d.Ci, d.Cip, kgi, col, j) : 0.f;
-    reinterpret_cast<T*>(d.dst)[li] = from_f<T>(v);
-  }
-}
-
-// ------------------------------------------------------------ fused AdamW + weight pack
-// The captured training step's optimizer launch (mmseg_adamw_pack_dev): the AdamW update of the whole flat arena
-// (adamw_one: mmseg_adamw_dev's per-element bits) with every packed weight's NEW value also written into its
-// operand images -- what mmseg_pack_conv3_batched / mmseg_pack_weights_batched would write from the updated fp32
-// weights at the next forward, which then skips its pack (one read of the fp32 weights and two launches less per
-// step).  Blocks by descriptor kind:
-//   0  3^3 conv: (8 co x 32 ci x 27 taps) tiles, pack_conv3_batched_kernel's tiles and image writes;
-//   1  1x1 / token linear W[Co][Ci] (pack modes 2 / 3) or transposed conv W[Ci][Co][8] (modes 4 / 5 / 7):
-//      8 source rows x up to AP_KT columns staged in LDS, written as 16-B vectors per image;
-//   2  a plain range of the arena (biases, norm / LayerNorm parameters, tables): the update only.
-// The host table (engine/layers.py Packer.adam_table) covers every arena element exactly once.  Entries no block
-// owns (K / channel padding) stay zero from allocation, as with the batched packs.
-constexpr int AP_KT = 512;      // kind-1 tile columns (a multiple of 64: whole 8-co groups of a transposed conv)
-constexpr int AP_RANGE = 4096;  // kind-2 elements per block
-struct AdamPackDesc {
-  void* d0;            // kind 0: forward image; kind 1: the mode0 image
-  void* d1;            // data-gradient image / the mode1 image (null: none)
-  long long off;       // first arena element of the weight (kind 0 / 1) or of the range (kind 2)
-  int kind, block_begin;
-  int R, K;            // kind 1: source rows x columns; kind 2: K = the range's length
-  int mode0, mode1;    // kind 1: pack modes of d0 / d1
-  int Co, Ci, Cip, Cpad, Cpad_d, Cop;   // kind 0: Pack3Desc's fields; kind 1: the weight's Co, Ci, Cpad / Cpad_d
-                                        // of d0 / d1, Cop of mode 7
-};
-
-// AdamW over `rows` runs of `len` arena elements (run r starts at a0 + r * stride); the new value of element
-// (r, i) goes to put(r, i, value).  float4 lanes when every run is 16-B aligned.
-template <typename PUT>
-__device__ __forceinline__ void ap_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, long long a0, long long stride, int rows, int len,
-                                          const AdamHyper& h, PUT&& put) {
-  const int tid = threadIdx.x;
-  if (((a0 | stride | (long long)len) & 3) == 0) {
-    const int n4 = len >> 2, tot = rows * n4;
-    for (int e = tid; e < tot; e += 256) {
-      const int r = e / n4, q = e - r * n4;
-      const long long k = ((a0 + r * stride) >> 2) + q;
-      float4 pv = reinterpret_cast<const float4*>(p)[k];
-      const float4 gv = reinterpret_cast<const float4*>(g)[k];
-      float4 mv = reinterpret_cast<const float4*>(m)[k];
-      float4 vv = reinterpret_cast<const float4*>(v)[k];
-      adamw_one(pv.x, gv.x, mv.x, vv.x, h);
-      adamw_one(pv.y, gv.y, mv.y, vv.y, h);
-      adamw_one(pv.z, gv.z, mv.z, vv.z, h);
-      adamw_one(pv.w, gv.w, mv.w, vv.w, h);
-      reinterpret_cast<float4*>(p)[k] = pv;
-      reinterpret_cast<float4*>(m)[k] = mv;
-      reinterpret_cast<float4*>(v)[k] = vv;
-      put(r, 4 * q, pv.x);
-      put(r, 4 * q + 1, pv.y);
-      put(r, 4 * q + 2, pv.z);
-      put(r, 4 * q + 3, pv.w);
-    }
-  } else {
-    const int tot = rows * len;
-    for (int e = tid; e < tot; e += 256) {
-      const int r = e / len, i = e - r * len;
-      const long long k = a0 + r * stride + i;
-      float pv = p[k], mv = m[k], vv = v[k];
-      adamw_one(pv, g[k], mv, vv, h);
-      p[k] = pv;
-      m[k] = mv;
-      v[k] = vv;
-      put(r, i, pv);
-    }
-  }
-}
-
-// one image of a kind-1 tile: s[8][AP_KT + 1] rows r0 .. r0 + 7, columns k0 .. k0 + kt (kt8: kt rounded up to 8,
-// zero past kt)
-template <typename T>
-__device__ __forceinline__ void ap_write1(const float (*s)[AP_KT + 1], int mode, void* dstp, int cpad, int Co, int Cop,
-                                          int r0, int k0, int kt, int kt8) {
-  const int tid = threadIdx.x;
-  T* dst = reinterpret_cast<T*>(dstp);
-  if (mode == 2) {            // 1x1 forward: (ci group, co) <- 8 ci of row co
-    for (int e = tid; e < kt8; e += 256) {
-      const int rr = e & 7, cg = e >> 3;
-      V8<T> w;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w.set(j, s[rr][cg * 8 + j]);
-      w.store(dst + ((long long)((k0 >> 3) + cg) * cpad + r0 + rr) * 8);
-    }
-  } else if (mode == 3) {     // 1x1 data gradient: (co group r0 / 8, ci) <- the tile's 8 rows of column ci
-    for (int c = tid; c < kt; c += 256) {
-      V8<T> w;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w.set(j, s[j][c]);
-      w.store(dst + ((long long)(r0 >> 3) * cpad + k0 + c) * 8);
-    }
-  } else if (mode == 4) {     // transposed forward: (ci group r0 / 8, t Co + co) <- 8 rows of column co 8 + t
-    const int ncol8 = kt >> 3;
-    for (int e = tid; e < kt; e += 256) {
-      const int t = e / ncol8, col = e - t * ncol8;
-      V8<T> w;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w.set(j, s[j][col * 8 + t]);
-      w.store(dst + ((long long)(r0 >> 3) * cpad + t * Co + (k0 >> 3) + col) * 8);
-    }
-  } else {                    // 5 / 7 transposed data gradient: (t Cop/8 + co group, ci) <- 8 co of row ci, tap t
-    const int cpgd = (mode == 7 ? Cop : Co) >> 3, ngrp = kt >> 6;
-    for (int e = tid; e < 64 * ngrp; e += 256) {
-      const int rr = e & 7, t = (e >> 3) & 7, cg = e >> 6;
-      V8<T> w;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w.set(j, s[rr][(cg * 8 + j) * 8 + t]);
-      const int co = (k0 >> 3) + cg * 8;
-      w.store(dst + ((long long)(t * cpgd + (co >> 3)) * cpad + r0 + rr) * 8);
-    }
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void adamw_pack_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v,
-                                                         const AdamPackDesc* __restrict__ descs, int n,
-                                                         AdamHyper hv, const AdamHyper* __restrict__ hp,
-                                                         const float* __restrict__ skip) {
-  __shared__ float sw[8][33][29];
-  AdamHyper h;
-  if (!adamw_load(hv, hp, skip, h)) return;
-  int lo = 0, hi = n - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (descs[mid].block_begin <= b) lo = mid;
-    else hi = mid - 1;
-  }
-  const AdamPackDesc d = descs[lo];
-  const int lb = b - d.block_begin;
-  const int tid = threadIdx.x;
-  if (d.kind == 0) {
-    const int nci = (d.Ci + 31) / 32;
-    const int co0 = (lb / nci) * 8, ci0 = (lb % nci) * 32;
-    const int cis = d.Ci - ci0 < 32 ? d.Ci - ci0 : 32;
-    if (co0 >= d.Co) return;
-    for (int e = tid; e < 8 * (32 - cis) * 27; e += 256) {   // the tile's channel padding reads as zero
-      const int co = e / ((32 - cis) * 27), r = e - co * ((32 - cis) * 27);
-      sw[co][cis + r / 27][r % 27] = 0.f;
-    }
-    ap_update(p, g, m, v, d.off + ((long long)co0 * d.Ci + ci0) * 27, (long long)d.Ci * 27, 8, cis * 27, h,
-              [&](int r, int i, float x) __attribute__((always_inline)) {
-                const int ci = i / 27;
-                sw[r][ci][i - ci * 27] = x;
-              });
-    __syncthreads();
-    pack3_write<T>(sw, d.d0, d.d1, d.Co, d.Cip, d.Cpad, d.Cpad_d, d.Cop, co0, ci0, cis);
-  } else if (d.kind == 1) {
-    float (*s)[AP_KT + 1] = reinterpret_cast<float (*)[AP_KT + 1]>(&sw[0][0][0]);
-    const int nkt = (d.K + AP_KT - 1) / AP_KT;
-    const int r0 = (lb / nkt) * 8, k0 = (lb % nkt) * AP_KT;
-    const int kt = d.K - k0 < AP_KT ? d.K - k0 : AP_KT, kt8 = (kt + 7) & ~7;
-    if (r0 >= d.R) return;
-    for (int e = tid; e < 8 * (kt8 - kt); e += 256) s[e / (kt8 - kt)][kt + e % (kt8 - kt)] = 0.f;
-    ap_update(p, g, m, v, d.off + (long long)r0 * d.K + k0, d.K, 8, kt, h,
-              [&](int r, int i, float x) __attribute__((always_inline)) { s[r][i] = x; });
-    __syncthreads();
-    ap_write1<T>(s, d.mode0, d.d0, d.Cpad, d.Co, d.Cop, r0, k0, kt, kt8);
-    if (d.d1 != nullptr) ap_write1<T>(s, d.mode1, d.d1, d.Cpad_d, d.Co, d.Cop, r0, k0, kt, kt8);
-  } else {
-    if (lb * AP_RANGE >= d.K) return;
-    const long long a0 = d.off + (long long)lb * AP_RANGE;
-    const int len = d.K - lb * AP_RANGE < AP_RANGE ? d.K - lb * AP_RANGE : AP_RANGE;
-    ap_update(p, g, m, v, a0, 0, 1, len, h, [](int, int, float) __attribute__((always_inline)) {});
   }
 }
 
@@ -5035,10 +3682,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
       if (mmseg::check_launch(c.name)) return 1;
       return c.reduce ? launch_splitk_reduce<T, MODE>(g, s) : 0;
     case GK_BRICK8:
-      if constexpr (sizeof(T) == 2) {
-        if (c.bn == 64) MMSEG_LAUNCH((conv3_brick8_kernel<64, 1>), grid, block, 0, s, g);
-        else MMSEG_LAUNCH((conv3_brick8_kernel<32, 2>), grid, block, 0, s, g);
-      }
+      if constexpr (sizeof(T) == 2) launch_brick8(g, c, s);
       break;
     case GK_BRICK2_BN48:
       if (c.b32) MMSEG_LAUNCH((conv3_brick2_kernel<T, 48, 1, false, true>), grid, block, 0, s, g);
@@ -5350,183 +3994,18 @@ int launch_wgrad_mode(const WgradArgs& g, const Conv3WgradChoice& c, int mode, h
   return 1;
 }
 
-// split slices S of a reduce: about 8 split loads per thread, the slice sums a pairwise
-// LDS tree; small gradients over many splits (the stem: 1,056 values x 1,024 splits) take more slices until the
-// grid fills the chip, down to 2 loads per thread (S = 64 left it at 66 blocks, 12.8 us for 4 MB)
-int wred_slices(const WReduceArgs& g) {
-  const int ksplit = g.ksplit;
-  const long long total = (long long)g.Ca * g.Ncols + (g.bias_part ? g.Ca : 0);
-  int S = 1;
-  while (S < 64 && ksplit / (2 * S) >= 8) S *= 2;
-  while (S < 256 && (total * S + 1023) / 1024 < 512 && ksplit / (2 * S) >= 2) S *= 2;
-  return S;
-}
-
-// reduces deferred by conv3_wgrad_impl (phase bit 4) until mmseg_wgrad_reduce_flush
-struct PendingWred {
-  WReduceArgs r;
-  int groups;
-  void* stream;
-};
-std::vector<PendingWred> g_wred_pending;
-extern "C" int mmseg_wgrad_reduce_flush(void* stream);
-
-// Queue a deferred reduce (summed by the next mmseg_wgrad_reduce_flush on its stream).  (Flushing early, once
-// 60-240 MB of partials are queued so they are re-read from the Infinity Cache, measured +0.03..0.12 ms: r04.)
-int wred_push(const WReduceArgs& r, int groups, void* stream) {
-  // a queued reduce reads its partials when the queue is flushed: a second weight-gradient kernel into the same
-  // partial buffer before that would have overwritten them (the engine flushes first: Runtime.own_part)
-  for (const auto& e : g_wred_pending)
-    if (e.stream == stream && (e.r.part == r.part || (r.bias_part && e.r.bias_part == r.bias_part))) {
-      mmseg::set_error("deferred weight-gradient reduce: its partial buffer is already queued on this stream "
-                       "(flush the queue before reusing it)");
-      return -1;
-    }
-  g_wred_pending.push_back({r, groups, stream});
-  return 0;
-}
-
-int launch_wgrad_reduce(WReduceArgs g, void* stream, int groups = 1) {
-  const long long total = (long long)g.Ca * g.Ncols + (g.bias_part ? g.Ca : 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int S = wred_slices(g);
-#define MMSEG_WRED(SS, NB)                                                                             \
-  case SS:                                                                                             \
-    MMSEG_LAUNCH((wgrad_reduce_kernel<SS, 4>), dim3(ceil_div(total, NB), groups), dim3(256), 0, s, g);  \
-    break;
-  switch (S) {
-    MMSEG_WRED(256, 4)
-    MMSEG_WRED(128, 8)
-    MMSEG_WRED(64, 16)
-    MMSEG_WRED(32, 32)
-    MMSEG_WRED(16, 64)
-    MMSEG_WRED(8, 128)
-    MMSEG_WRED(4, 256)
-    MMSEG_WRED(2, 512)
-    default:
-      MMSEG_WRED(1, 1024)
-  }
-#undef MMSEG_WRED
-  return mmseg::check_launch("wgrad_reduce");
-}
-
 }  // namespace
-
-// e4m3 B-operand image of a 3^3 conv for brick6 F8 ([KGp][Cpad][8] bytes, the bf16 image's geometry): one block
-// per output channel: s = 448 / max |w[co]| (1 for an all-zero row; 448 = e4m3fn's largest finite value), the
-// entries w[co][ci][tap] * s rounded to e4m3 (v_cvt_pk_fp8_f32: round to nearest even), wdq[co] = 1 / s.
-__global__ __launch_bounds__(256) void pack_conv3_fp8_kernel(const float* __restrict__ w, int Ci, int Cip, int Cpad,
-                                                             unsigned char* __restrict__ dst, float* __restrict__ wdq) {
-  const int co = blockIdx.x, tid = threadIdx.x;
-  const int n = Ci * 27;
-  const float* wr = w + (long long)co * n;
-  float m = 0.f;
-  for (int e = tid; e < n; e += 256) m = fmaxf(m, fabsf(wr[e]));
-  __shared__ float red[4];
-  m = fmaxf(m, __shfl_xor(m, 1, 64));
-#pragma unroll
-  for (int o = 2; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float sc = m > 0.f ? 448.f / m : 1.f;
-  if (tid == 0) wdq[co] = 1.f / sc;
-  for (int e = tid; e < n; e += 256) {
-    const int ci = e / 27, tap = e - ci * 27;
-    const int kgi = tap * (Cip / 8) + ci / 8;
-    const int v = __builtin_amdgcn_cvt_pk_fp8_f32(wr[e] * sc, 0.f, 0, false);
-    dst[((long long)kgi * Cpad + co) * 8 + (ci & 7)] = (unsigned char)(v & 0xff);
-  }
-}
 
 // =================================================================== C ABI
 extern "C" {
 
-// Pack fp32 torch-layout weights into the MFMA B-operand layout [KGp][Cpad][8].
-int mmseg_pack_weight(const float* w, void* dst, int mode, int Co, int Ci, int Cip, int KG, int KGp, int Cpad,
-                      int dtype, void* stream) {
-  PackArgs g{w, dst, Co, Ci, Cip, KG, KGp, Cpad};
-  long long total = (long long)KGp * Cpad * 8;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MMSEG_BF16)
-    MMSEG_LAUNCH(pack_weight_kernel<bf16_t>, dim3(ceil_div(total, 256)), dim3(256), 0, s, g, mode);
-  else
-    MMSEG_LAUNCH(pack_weight_kernel<float>, dim3(ceil_div(total, 256)), dim3(256), 0, s, g, mode);
-  return mmseg::check_launch("pack_weight");
-}
-
-int mmseg_pack3_desc_bytes(void) { return (int)sizeof(Pack3Desc); }
-
-int mmseg_adamw_pack_desc_bytes(void) { return (int)sizeof(AdamPackDesc); }
-
-static int adamw_pack_launch(float* p, const float* g, float* m, float* v, const void* descs, int n, int nblocks,
-                             const AdamHyper& hv, const AdamHyper* hp, const float* skip, int dtype,
-                             hipStream_t s) {
-  MMSEG_REQUIRE(n >= 1 && nblocks >= 1 && descs != nullptr, "adamw_pack: a descriptor table (Packer.adam_table)");
-  MMSEG_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                  reinterpret_cast<uintptr_t>(v)) & 15) == 0, "adamw_pack: p, g, m, v must be 16-B aligned");
-  if (dtype == MMSEG_BF16)
-    MMSEG_LAUNCH(adamw_pack_kernel<bf16_t>, dim3(nblocks), dim3(256), 0, s, p, g, m, v, (const AdamPackDesc*)descs,
-                 n, hv, hp, skip);
-  else
-    MMSEG_LAUNCH(adamw_pack_kernel<float>, dim3(nblocks), dim3(256), 0, s, p, g, m, v, (const AdamPackDesc*)descs,
-                 n, hv, hp, skip);
-  return mmseg::check_launch("adamw_pack");
-}
-
-// descs: device array of n AdamPackDesc sorted by block_begin, nblocks blocks in all (Packer.adam_table); the
-// step's hyper-parameters by value (as mmseg_adamw) or as the 8 device floats of mmseg_adamw_hyper (as
-// mmseg_adamw_dev); skip as there.  p / g / m / v: the flat arenas, 16-B aligned.
-int mmseg_adamw_pack(float* p, const float* g, float* m, float* v, const void* descs, int n, int nblocks, float lr,
-                     float beta1, float beta2, float eps, float wd, int step, const float* skip, int dtype,
-                     void* stream) {
-  MMSEG_REQUIRE(step >= 1, "adamw_pack: step counts from 1");
-  return adamw_pack_launch(p, g, m, v, descs, n, nblocks, adamw_hyper(lr, beta1, beta2, eps, wd, step), nullptr, skip,
-                           dtype, (hipStream_t)stream);
-}
-
-int mmseg_adamw_pack_dev(float* p, const float* g, float* m, float* v, const void* descs, int n, int nblocks,
-                         const float* hyper, const float* skip, int dtype, void* stream) {
-  MMSEG_REQUIRE(hyper != nullptr, "adamw_pack_dev: hyper (8 device floats from mmseg_adamw_hyper) required");
-  return adamw_pack_launch(p, g, m, v, descs, n, nblocks, AdamHyper{}, reinterpret_cast<const AdamHyper*>(hyper),
-                           skip, dtype, (hipStream_t)stream);
-}
-
 #ifdef MMSEG_TIMING_PROBES
 // probe builds only (tools/convbench.py --probe): buffer of 8 * PROBE_NB + 32 * 16 * 64 longs, or null to stop
 int mmseg_probe_set(long long* buf) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_probe), &buf, sizeof(buf)) == hipSuccess ? 0 : 1;
+  const int own = hipMemcpyToSymbol(HIP_SYMBOL(g_probe), &buf, sizeof(buf)) == hipSuccess ? 0 : 1;
+  return own | probe_set_brick6(buf) | probe_set_brick8(buf);   // (every source has its own g_probe)
 }
 #endif
-
-// descs: device array of n Pack3Desc sorted by block_begin; nblocks = total blocks
-// (sum over layers of Co/8 * ceil(Ci/32)).  The images must be zero-initialised once.
-int mmseg_pack_conv3_batched(const void* descs, int n, int nblocks, int dtype, void* stream) {
-  MMSEG_REQUIRE(n >= 1 && nblocks >= 1, "pack_conv3_batched: empty table");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MMSEG_BF16)
-    MMSEG_LAUNCH(pack_conv3_batched_kernel<bf16_t>, dim3(nblocks), dim3(256), 0, s, (const Pack3Desc*)descs, n);
-  else
-    MMSEG_LAUNCH(pack_conv3_batched_kernel<float>, dim3(nblocks), dim3(256), 0, s, (const Pack3Desc*)descs, n);
-  return mmseg::check_launch("pack_conv3_batched");
-}
-
-// descs: device array of n PackDesc (64 B each, see mmseg_pack_desc_bytes); total = sum of KGp*Cpad*8.
-int mmseg_pack_desc_bytes(void) { return (int)sizeof(PackDesc); }
-
-int mmseg_pack_weights_batched(const void* descs, int n, long long total, int dtype, void* stream) {
-  MMSEG_REQUIRE(n >= 1, "pack_weights_batched: n >= 1");
-  hipStream_t s = (hipStream_t)stream;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (dtype == MMSEG_BF16)
-    MMSEG_LAUNCH(pack_weight_batched_kernel<bf16_t>, dim3((int)blocks), dim3(256), 0, s, (const PackDesc*)descs,
-                       n, total);
-  else
-    MMSEG_LAUNCH(pack_weight_batched_kernel<float>, dim3((int)blocks), dim3(256), 0, s, (const PackDesc*)descs,
-                       n, total);
-  return mmseg::check_launch("pack_weights_batched");
-}
 
 // Generic implicit-GEMM: conv3 fwd / dgrad, 1x1, convT fwd / dgrad.
 // cin_real: the A source's channels past cin_real are padding (zero weights), so the CONV3 brick kernels skip the
@@ -5676,16 +4155,6 @@ int mmseg_conv3_fp8_ok(int M, int Ncols, int Cpad, int KG, int cpg_shift, int D,
   return choose_conv3(M, Ncols, Cpad, KG, cpg_shift, D, H, W, lda, ldo, MMSEG_BF16, CF_FP8).kernel == GK_BRICK6;
 }
 
-int mmseg_pack_conv3_fp8(const float* w, int Co, int Ci, int Cip, int KGp, int Cpad, void* dst, float* wdq,
-                         void* stream) {
-  MMSEG_REQUIRE(w && dst && wdq && Co > 0 && Co <= Cpad && Ci <= Cip && Cip % 8 == 0 && KGp * 8 >= 27 * Cip,
-                "pack_conv3_fp8: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  hipMemsetAsync(dst, 0, (size_t)KGp * Cpad * 8, s);   // K / column padding stays e4m3 zero
-  MMSEG_LAUNCH(pack_conv3_fp8_kernel, dim3(Co), dim3(256), 0, s, w, Ci, Cip, Cpad, (unsigned char*)dst, wdq);
-  return mmseg::check_launch("pack_conv3_fp8");
-}
-
 // out = conv3(A) with e4m3 operands (A: bf16 NDHWC, staged as e4m3; with nmean / nrstd: relu((a - mean) * rstd)
 // first, as mmseg_conv3_fwd_norm), bf16 output; w8 / wdq from mmseg_pack_conv3_fp8 (requires mmseg_conv3_fp8_ok).
 int mmseg_conv3_fwd_fp8(const void* a, int lda, const float* nmean, const float* nrstd, const void* w8,
@@ -5788,23 +4257,6 @@ int mmseg_wgrad(const void* a, int lda, const void* b, int ldb, float* part, flo
 // Effective split count the wgrad launcher will use (callers size `part` with it).
 int mmseg_wgrad_splits(long long V, int ksplit) { return mmseg_wgrad_splits_impl(V, ksplit); }
 
-int mmseg_wgrad_reduce(const float* part, float* grad, const float* bias_part, float* bias_grad, int Ca, int Ncols,
-                       int ksplit, int cpad, int creal, int ntap, int accumulate, void* stream) {
-  MMSEG_REQUIRE(((long long)Ca * Ncols) % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0,
-                "wgrad_reduce: Ca*Ncols %% 4 == 0 and a 16-B aligned partial buffer");
-  WReduceArgs g{part, grad, bias_part, bias_grad, Ca, Ncols, ksplit, cpad, creal, ntap, accumulate, 0};
-  return launch_wgrad_reduce(g, stream);
-}
-
-// mmseg_wgrad_reduce queued until mmseg_wgrad_reduce_flush(stream) (part must stay untouched until then)
-int mmseg_wgrad_reduce_defer(const float* part, float* grad, const float* bias_part, float* bias_grad, int Ca,
-                             int Ncols, int ksplit, int cpad, int creal, int ntap, int accumulate, void* stream) {
-  MMSEG_REQUIRE(((long long)Ca * Ncols) % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0,
-                "wgrad_reduce: Ca*Ncols %% 4 == 0 and a 16-B aligned partial buffer");
-  WReduceArgs g{part, grad, bias_part, bias_grad, Ca, Ncols, ksplit, cpad, creal, ntap, accumulate, 0};
-  return wred_push(g, 1, stream);
-}
-
 // Weight (+ bias) gradient of a 3^3 conv straight into the torch-layout fp32 gradient
 // grad[Co][Ci][27] (+ bias_grad[Co]), = or += (accumulate).  The library picks kernel and split;
 // ws holds mmseg_conv3_wgrad_ws_floats() floats (more lets it split further, fewer is clamped).
@@ -5885,60 +4337,6 @@ int mmseg_conv3_wgrad_ex(const void* dy, int lddy, const void* x, int ldx, const
                 "conv3_wgrad_ex: unsupported shape for the deferred norm (mmseg_conv3_wgrad_norm_ok)");
   return conv3_wgrad_impl(dy, lddy, x, ldx, nmean, nrstd, grad, bias_grad, Co, Cip, Ci, cpg_shift, V, D, H, W, ws,
                           ws_floats, accumulate, dtype, stream, phase);
-}
-
-// Launch the reduces deferred with phase bit 4 (in the order they were deferred, at most WRB_MAX per launch) on
-// `stream`; each gradient is bitwise what its own reduce would have written.  Returns the number flushed.
-int mmseg_wgrad_reduce_flush(void* stream) {
-  int done = 0;
-  std::vector<PendingWred> keep;
-  std::vector<PendingWred> mine;
-  for (auto& e : g_wred_pending) (e.stream == stream ? mine : keep).push_back(e);
-  g_wred_pending.swap(keep);
-  for (size_t i0 = 0; i0 < mine.size(); i0 += 0) {
-    WReduceBatch b{};
-    // at most WRB_MAX per launch, and a gradient written by two queued reduces (an accumulating second use) starts
-    // a new launch, so the two stay ordered
-    size_t i1 = i0;
-    while (i1 < mine.size() && i1 - i0 < (size_t)WRB_MAX) {
-      bool clash = false;
-      for (size_t j = i0; j < i1; ++j)
-        clash = clash || mine[j].r.grad == mine[i1].r.grad ||
-                (mine[i1].r.bias_grad != nullptr && mine[j].r.bias_grad == mine[i1].r.bias_grad);
-      if (clash) break;
-      ++i1;
-    }
-    b.n = (int)(i1 - i0);
-    int blk = 0;
-    for (int k = 0; k < b.n; ++k) {
-      const PendingWred& e = mine[i0 + k];
-      const long long total = (long long)e.r.Ca * e.r.Ncols + (e.r.bias_part ? e.r.Ca : 0);
-      b.d[k] = e.r;
-      b.S[k] = wred_slices(e.r);
-      b.nbx[k] = ceil_div(total, 1024 / b.S[k]);
-      b.blk0[k] = blk;
-      blk += b.nbx[k] * e.groups;
-    }
-    b.blk0[b.n] = blk;
-    mmseg::note_kernel("wgrad_reduce_batch_kernel");
-    MMSEG_LAUNCH(wgrad_reduce_batch_kernel, dim3(blk), dim3(256), 0, (hipStream_t)stream, b);
-    if (mmseg::check_launch("wgrad_reduce_batch")) return -1;
-    done += b.n;
-    i0 = i1;
-  }
-  return done;
-}
-
-// number of deferred reduces not yet flushed (all streams)
-int mmseg_wgrad_reduce_pending(void) { return (int)g_wred_pending.size(); }
-
-// drop the deferred reduces of `stream` (a backward that failed half way); returns how many
-int mmseg_wgrad_reduce_discard(void* stream) {
-  const size_t n0 = g_wred_pending.size();
-  g_wred_pending.erase(std::remove_if(g_wred_pending.begin(), g_wred_pending.end(),
-                                      [&](const PendingWred& e) { return e.stream == stream; }),
-                       g_wred_pending.end());
-  return (int)(n0 - g_wred_pending.size());
 }
 
 int conv3_wgrad_impl(const void* dy, int lddy, const void* x, int ldx, const float* nmean, const float* nrstd,

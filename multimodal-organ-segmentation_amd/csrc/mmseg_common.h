@@ -176,7 +176,7 @@ __device__ __forceinline__ float mmseg_gelu_grad(float x) {
 // [decay, omb1, beta2, omb2, eps, step_size, bc2_sqrt, unused].  `skip` (nullable): a device float, the
 // step's count of out-of-range labels (summed over the ranks under DP); non-zero leaves p, m, v untouched,
 // so a batch the trainer is about to raise on never updates the model.  Shared by the AdamW kernels
-// (loss_head.hip) and the fused AdamW + weight pack (conv_gemm.hip): one per-element formula, one set of bits.
+// (loss_head.hip) and the fused AdamW + weight pack (conv_pack.hip): one per-element formula, one set of bits.
 struct AdamHyper {
   float decay, omb1, beta2, omb2, eps, step_size, bc2_sqrt, pad;
 };

@@ -110,7 +110,7 @@ class Packer:
             self.gtable = torch.frombuffer(gblob, dtype=torch.uint8).to(rt.device)
             self.gn, self.gtotal = len(rest), total
 
-    AP_KT, AP_RANGE = 512, 4096   # conv_gemm.hip: kind-1 tile columns, kind-2 elements per block
+    AP_KT, AP_RANGE = 512, 4096   # conv_pack.hip: kind-1 tile columns, kind-2 elements per block
 
     def adam(self, flat) -> Optional[Tuple[torch.Tensor, int, int]]:
         """adam_table(flat), built once per arena."""

@@ -1,4 +1,4 @@
-"""The fused AdamW + weight pack (mmseg_adamw_pack / _dev, conv_gemm.hip adamw_pack_kernel) against the two
+"""The fused AdamW + weight pack (mmseg_adamw_pack / _dev, conv_pack.hip adamw_pack_kernel) against the two
 launches it replaces: mmseg_adamw over the arena, then the engine's batched packs (layers.Packer.run) from the
 updated fp32 weights.  Parameters, moments and every operand image must be BITWISE equal -- on UNet3D /
 DualEncoder (3^3 conv tiles, transposed convs) and SwinUNETR (token linears, patch embedding, transposed convs,

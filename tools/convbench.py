@@ -7,7 +7,7 @@ Ops: fwd, fwdn (forward of relu(IN(x)) with the norm applied on staging: Block.d
 (data gradient that also sums the InstanceNorm-backward partials of its output: Block.bwd's conv2 at 96^3), wgrad,
 wgradn (weight gradient with the deferred norm of x).
 --probe: load libmmseg_hip_probe.so (make -C csrc probe) and print the block timeline of one launch per op
-(per-CU residency, block lifetimes, per-phase cycles of block 0's waves; see conv_gemm.hip PROBE_*).
+(per-CU residency, block lifetimes, per-phase cycles of block 0's waves; see conv_common.h PROBE_*).
 """
 import argparse
 import json

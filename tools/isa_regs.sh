@@ -1,5 +1,5 @@
 # VGPR / spill counts of the gfx950 kernels in one built object whose mangled name contains PATTERN.
-# usage: bash tools/isa_regs.sh conv_gemm PATTERN   (reads multimodal-organ-segmentation_amd/csrc/build/<src>.hip.o)
+# usage: bash tools/isa_regs.sh SRC PATTERN   (SRC: conv_gemm, conv_brick6, conv_brick8, conv_pack, wgrad_reduce, ...; reads multimodal-organ-segmentation_amd/csrc/build/<src>.hip.o)
 set -e
 SRC=${1:-conv_gemm}; PAT=${2:-.}
 R=$(cd "$(dirname "$0")/.." && pwd)
