@@ -526,6 +526,28 @@ int mmseg_window_accum(const float* logits, int N, int C, int D, int H, int W, i
                        int r1, int r2, float* out, void* stream);
 int mmseg_window_norm(float* out, int N, int C, int D, int H, int W, const float* cz, const float* cy, const float* cx,
                       void* stream);
+/* Weighted blending and flip test-time augmentation (opt-in; the three entry points above stay the constant,
+ * no-TTA path).  flip: bit d mirrors axis d of (r0, r1, r2) inside each window (bits above 2 are rejected).
+ * gather_flip: mmseg_window_gather, then the flip (the zero padding is part of the window that is flipped).
+ * tta_accum: acc[rows][r0][r1][r2] (assign ? = : +=) pred un-flipped, then * scale (1 / flips on the last one).
+ * window_blend: out[n][c][v] += w * pred[k][c][..], count[n][v] += w for the nw windows of one predictor batch;
+ *   win_host is a HOST int[4*nw] = (n, z0, y0, x0).  Output-stationary: one thread owns a voxel and walks the
+ *   windows that cover it in increasing index, so each voxel's sums have MONAI's fp32 addition order (w * pred
+ *   is rounded before the add).  blend 0: w = 1; blend 1: w = max((gz[z] * gy[y]) * gx[x], wmin) with the
+ *   per-axis tables gz [r0], gy [r1], gx [r2] on the device.  count is [N][D][H][W].
+ * window_finish: out[n][c][v] /= count[n][v].
+ * blend_argmax_encode: mmseg_argmax_encode of out[c] / count for one volume (out [C][X][Y][Z], count [X][Y][Z])
+ *   without writing the quotient: bitwise the mask of window_finish followed by argmax_encode. */
+int mmseg_window_gather_flip(const float* vol, int N, int C, int D, int H, int W, const int* win, int nw, int r0,
+                             int r1, int r2, int flip, float* out, void* stream);
+int mmseg_tta_accum(const float* pred, long long rows, int r0, int r1, int r2, int flip, int assign, float scale,
+                    float* acc, void* stream);
+int mmseg_window_blend(const float* pred, int N, int C, int D, int H, int W, const int* win_host, int nw, int r0,
+                       int r1, int r2, int blend, const float* gz, const float* gy, const float* gx, float wmin,
+                       float* out, float* count, void* stream);
+int mmseg_window_finish(float* out, const float* count, int N, int C, long long V, void* stream);
+int mmseg_blend_argmax_encode(const float* out, const float* count, int C, int X, int Y, int Z, unsigned char* mask,
+                              void* stream);
 
 /* ------------------------------------------------- head, loss, metric */
 /* NCDHW fp32 volume channels [c0, c0+cnt) -> NDHWC 8-channel engine layout

@@ -6,6 +6,7 @@ with a message.
     python main.py --mode train --config configs/c2_unet_96_bf16.yaml
     python main.py --mode inference --config configs/c6_unet_nifti.yaml --checkpoint outputs/c6_unet_nifti/best.pth \
         --input data/new_cases --output outputs/predictions
+    python main.py --mode inference ... --blend gaussian --tta-flips 0 1 2     (Gaussian blending, 8 mirrored passes)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode train \
         --config configs/c3_dual_encoder_96_dp.yaml
 """
@@ -43,6 +44,11 @@ def parse_args(argv=None):
     p.add_argument("--fusion", default=None, choices=["early", "late", "attention", "cross_attention"])
     p.add_argument("--modalities", nargs="+", default=None)
     p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--blend", default=None, choices=["constant", "gaussian"],
+                   help="inference: window blending (inference.sliding_window.blend)")
+    p.add_argument("--tta-flips", nargs="*", type=int, default=None, choices=[0, 1, 2],
+                   help="inference: axes (0, 1, 2 = D, H, W of the volume) mirrored for test-time augmentation "
+                        "(inference.tta_flips)")
     p.add_argument("--verbose", "-v", action="store_true")
     p.add_argument("--debug", action="store_true")
     return p.parse_args(argv)
@@ -73,6 +79,10 @@ def merge_config_with_args(config, args):
         md.setdefault("fusion", {})["type"] = args.fusion
     if args.modalities is not None:
         config["data"]["modalities"] = args.modalities
+    if args.blend is not None:
+        config.setdefault("inference", {}).setdefault("sliding_window", {})["blend"] = args.blend
+    if args.tta_flips is not None:
+        config.setdefault("inference", {})["tta_flips"] = list(args.tta_flips)
     config["_args"] = {"mode": args.mode, "input": args.input, "output": args.output, "checkpoint": args.checkpoint,
                        "resume": args.resume, "verbose": args.verbose, "debug": args.debug}
     return config

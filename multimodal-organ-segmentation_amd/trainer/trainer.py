@@ -484,7 +484,9 @@ class Trainer:
         The volumes are decoded on the device, the windows run there, and the argmax is fused with the
         permutation back to file order (mmseg_argmax_encode), so X*Y*Z bytes per case return to the host.
         Like the reference, the windows see the RAW volume -- training normalises, this does not (DESIGN.md
-        "Semantics traps"); inference.normalize: true applies DeviceModalityNormalize first.  Under data
+        "Semantics traps"); inference.normalize: true applies DeviceModalityNormalize first.  With
+        inference.sliding_window.blend: gaussian or inference.tta_flips the mask comes straight from the blend
+        accumulators (mmseg_blend_argmax_encode); with neither, the calls are the ones above.  Under data
         parallelism rank 0 predicts."""
         if self.rank != 0:
             return
@@ -503,8 +505,12 @@ class Trainer:
                 image, first = load_modalities(paths, stager)
                 if norm is not None:
                     norm(image)
-                logits = self._sliding_window_inference(image.unsqueeze(0))
-                mask = argmax_encode(logits[0].float()).cpu().numpy().reshape(first.shape, order="F")
+                if self._blend_options() is None:
+                    logits = self._sliding_window_inference(image.unsqueeze(0))
+                    mask = argmax_encode(logits[0].float())
+                else:       # gaussian blending / flip TTA: the division is fused into the argmax
+                    mask = self._sliding_window_mask(image.unsqueeze(0))
+                mask = mask.cpu().numpy().reshape(first.shape, order="F")
                 save_nifti(mask, output_path / f"{case_id}_pred.nii.gz", first.affine)
                 if self.logger:
                     self.logger.info(f"Predicted {case_id}: {tuple(first.shape)} -> {case_id}_pred.nii.gz")
@@ -513,12 +519,34 @@ class Trainer:
         """reference trainer.py:370-395: MONAI sliding_window_inference(image, roi_size, sw_batch_size=
         inference.batch_size, predictor=model, overlap) on device (inference/sliding_window.py).  The
         reference's ImportError fallback (one full-volume forward) is not taken: the device restatement
-        always exists."""
+        always exists.  inference.sliding_window.blend / sigma_scale and inference.tta_flips opt into Gaussian
+        blending and flip test-time augmentation; the reference's `mode` and `tta` keys stay ignored."""
         from ..inference import sliding_window_inference
         inf = self.config.get("inference", {})
         sw = inf.get("sliding_window", {})
         return sliding_window_inference(image.to(self.device), tuple(sw.get("roi_size", (96, 96, 96))),
-                                        int(inf.get("batch_size", 4)), self.model, float(sw.get("overlap", 0.5)))
+                                        int(inf.get("batch_size", 4)), self.model, float(sw.get("overlap", 0.5)),
+                                        **(self._blend_options() or {}))
+
+    def _blend_options(self):
+        """The opt-in keys as keyword arguments of the batched path, or None when both are at their defaults
+        (constant blending, no flips: the per-window path)."""
+        inf = self.config.get("inference", {})
+        sw = inf.get("sliding_window", {})
+        blend, flips = sw.get("blend", "constant"), tuple(inf.get("tta_flips") or ())
+        if blend == "constant" and not flips:
+            return None
+        return {"blend": blend, "sigma_scale": float(sw.get("sigma_scale", 0.125)), "tta_flips": flips}
+
+    def _sliding_window_mask(self, image: torch.Tensor) -> torch.Tensor:
+        """One volume [1, M, X, Y, Z] -> its class mask in file order, from the blend accumulators."""
+        from ..inference import blend_argmax_encode, sliding_window_accumulate
+        inf = self.config.get("inference", {})
+        sw = inf.get("sliding_window", {})
+        out, count = sliding_window_accumulate(image.to(self.device), tuple(sw.get("roi_size", (96, 96, 96))),
+                                               int(inf.get("batch_size", 4)), self.model,
+                                               float(sw.get("overlap", 0.5)), **self._blend_options())
+        return blend_argmax_encode(out[0], count[0])
 
     def _save_checkpoints(self, metrics: Dict[str, float]) -> None:
         """reference trainer.py:397-433 (rank 0 only)."""
