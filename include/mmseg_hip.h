@@ -349,9 +349,14 @@ int mmseg_fuse_norm_fwd(const void* const* srcs, const int* lds, const float* co
 int mmseg_fuse_pool_fwd(const void* const* srcs, const int* lds, const float* const* means, const float* const* rstds,
                         int M, float wconst, void* out, int ldo, void* const* ys, const int* ldys,
                         uint8_t* const* idxs, int N, int D, int H, int W, int C, int dtype, void* stream);
-/* CrossModalAttention gate: Linear -> ReLU -> Linear -> softmax (dual_encoder.py:226-233). */
+/* CrossModalAttention gate: Linear -> ReLU -> Linear -> softmax (dual_encoder.py:226-233).  pooled [N][MC], W1
+ * [Hd][MC], W2 [M][Hd]; writes hbuf [N][Hd] and wts [N][M].  1 <= M <= 4; Hd floats of dynamic LDS (<= 64 KB). */
 int mmseg_attn_gate_fwd(const float* pooled, const float* W1, const float* b1, const float* W2, const float* b2,
                         float* hbuf, float* wts, int N, int MC, int Hd, int M, void* stream);
+/* Its backward, from dfused (the fused tensor's gradient) and the M sources: beta [N][M C] = dpooled / V (the beta of
+ * mmseg_instnorm_relu_bwd) and the Linear gradients (accumulate: added to what is there).  One 256-thread block
+ * finishes the gate: 1 <= M <= 4, N * M <= 256 and (N * M + N * Hd) floats of dynamic LDS (<= 64 KB); no operand may
+ * be NULL.  ws holds 4 * 256 * N floats (up to 256 dot-product chunks per sample, 4 sources each). */
 int mmseg_attn_gate_bwd(const void* const* srcs, const int* lds, int M, const void* dfused, int ldd, int N, long long V,
                         int C, const float* pooled, const float* W1, const float* W2, const float* hbuf,
                         const float* wts, float* beta, float* gW1, float* gb1, float* gW2, float* gb2, int Hd,

@@ -1472,6 +1472,9 @@ __global__ void attn_gate_bwd(const float* __restrict__ dot_part, int nchunk, co
 // item count must stay that far below INT_MAX so the last i += stride cannot wrap negative.
 constexpr long long kGridStrideMax = 2147483647LL - 8192LL * 256;
 
+// dynamic LDS a gate kernel may ask for (a launch over the 64 KB default limit fails)
+constexpr long long kGateLdsBytes = 64 * 1024;
+
 int grid_for(long long total) {
   long long b = (total + 255) / 256;
   if (b > 8192) b = 8192;
@@ -1979,7 +1982,10 @@ int mmseg_fuse_pool_fwd(const void* const* srcs, const int* lds, const float* co
 
 int mmseg_attn_gate_fwd(const float* pooled, const float* W1, const float* b1, const float* W2, const float* b2,
                         float* hbuf, float* wts, int N, int MC, int Hd, int M, void* stream) {
-  MMSEG_REQUIRE(M <= 4, "attn gate: M <= 4");
+  MMSEG_REQUIRE(M >= 1 && M <= 4, "attn gate: M=%d outside [1, 4]", M);
+  MMSEG_REQUIRE(N > 0 && MC > 0 && Hd > 0, "attn gate: N=%d, MC=%d, Hd=%d must be positive", N, MC, Hd);
+  MMSEG_REQUIRE((long long)Hd * (long long)sizeof(float) <= kGateLdsBytes, "attn gate: Hd=%d floats exceed the LDS", Hd);
+  MMSEG_REQUIRE(pooled && W1 && b1 && W2 && b2 && hbuf && wts, "attn gate: null operand");
   MMSEG_LAUNCH(attn_gate_fwd, dim3(N), dim3(256), Hd * sizeof(float), (hipStream_t)stream, pooled, W1, b1, W2,
                      b2, hbuf, wts, MC, Hd, M);
   return mmseg::check_launch("attn_gate_fwd");
@@ -1991,7 +1997,17 @@ int mmseg_attn_gate_bwd(const void* const* srcs, const int* lds, int M, const vo
                         int C, const float* pooled, const float* W1, const float* W2, const float* hbuf,
                         const float* wts, float* beta, float* gW1, float* gb1, float* gW2, float* gb2, int Hd,
                         float* ws, int accumulate, int dtype, void* stream) {
-  MMSEG_REQUIRE(M <= 4 && C % 8 == 0, "attn gate bwd: M <= 4");
+  MMSEG_REQUIRE(M >= 1 && M <= 4 && C > 0 && C % 8 == 0, "attn gate bwd: M=%d outside [1, 4] or C=%d no multiple of 8", M,
+                C);
+  MMSEG_REQUIRE(N > 0 && V > 0 && Hd > 0, "attn gate bwd: N=%d, V=%lld, Hd=%d must be positive", N, V, Hd);
+  // attn_gate_bwd is ONE 256-thread block: thread n * M + m owns dlogit[n][m], and dlogit / dh live in dynamic LDS
+  MMSEG_REQUIRE((long long)N * M <= 256, "attn gate bwd: N*M=%lld exceeds the 256 threads of the gate block",
+                (long long)N * M);
+  MMSEG_REQUIRE(((long long)N * M + (long long)N * Hd) * (long long)sizeof(float) <= kGateLdsBytes,
+                "attn gate bwd: (N*M + N*Hd) floats exceed the LDS (N=%d, M=%d, Hd=%d)", N, M, Hd);
+  MMSEG_REQUIRE(srcs && lds && dfused && pooled && W1 && W2 && hbuf && wts && beta && gW1 && gb1 && gW2 && gb2 && ws,
+                "attn gate bwd: null operand");
+  for (int m = 0; m < M; ++m) MMSEG_REQUIRE(srcs[m], "attn gate bwd: source %d is null", m);
   FuseSrc s{};
   for (int m = 0; m < M; ++m) {
     s.p[m] = srcs[m];
