@@ -657,6 +657,40 @@ int mmseg_confusion_counts_idx(const void* pred, int pred_bytes, const void* tar
                                int C, long long* counts, unsigned long long* invalid, void* stream);
 int mmseg_confusion_counts(const float* logits, const void* target, int target_bytes, int N, int C, long long V,
                            long long* counts, unsigned long long* invalid, void* stream);
+/* ------------------------------------------------------- SUV / TMTV / histogram analysis */
+/* The statistics of the reference's SUVAnalyzer, TMTVAnalyzer and HistogramAnalyzer (src/analysis/suv.py:76-105 and
+ * 147-167, tmtv.py:111-301, histogram.py:103-143 and 202-286) over one case, in one call that only enqueues on
+ * `stream`.  suv, seg: the files' raw voxel blocks in file order (x fastest), read as mmseg_nifti_decode reads them
+ * (*_datatype one of the eight NIfTI-1 codes, *_swap, *_scale with slope / inter in two roundings); seg null = no
+ * segmentation, every voxel in tumor_region.  The label is the decoded double truncated toward zero
+ * (get_fdata().astype(np.int32)).  Slots: 1..organ_max the organs (organ_max <= 15), 0 = label 0 or > organ_max
+ * (tumor_region), organ_max + 1 = negative labels (used only for the whole-volume maximum).  A non-finite SUV voxel
+ * is counted in `invalid` and enters no statistic.
+ * curve_rel, curve_abs: ncurve (<= 63) ascending thresholds each on the device, np.linspace(0, 1, 50) (non-negative
+ * fractions of the organ's maximum) and np.linspace(0, 20, 50).  bins <= 256.  masks: nullable, 3 * V uint8 in
+ * file order: absolute, percentage, liver-based (_create_tmtv_mask; the absolute threshold when the liver is absent).
+ * record: mmseg_suv_record_cells() 8-byte cells, doubles unless marked u64:
+ *   0 invalid u64 | 1..4 absolute mask: count u64, sum, max, mean | 5 percentage threshold (max_region *
+ *   pct_thr), 6..9 its mask: count u64, sum, max, mean | 10 liver present u64, 11 liver mask threshold
+ *   (mean + 2 std, uncontracted), 12..15 its mask: count u64, sum, max, mean, 16 liver mean, 17 liver std |
+ *   18 u64 C-order index (x Y + y) Z + z of the absolute mask's first maximum (np.argmax), ~0 when it is empty,
+ *   19 SUVpeak: np.mean over the +-3 box around it, clipped, all voxels | 20..25 analyze_tumor's mask
+ *   (label <= 0 and x >= tumor_thr): count u64, sum, max, mean, a[(n-1)/2], a[n/2] | 26 max_region
+ *   32 + 8 s, slot s < 17: count u64, min, max, sum, mean, sum (x - mean)^2, std (sqrt(m2 / n))
+ *   168 + 8 o, organ o = label - 1: counts of x >= max * {0.4, 0.5, 0.6} u64 x 3, a[(n-1)/2], a[n/2] (sorted
+ *     values; np.median is their mean), histogram range lo, hi (min, max; -+0.5 when equal)
+ *   288 + 64 o + j: u64 count of x >= max_o * curve_rel[j];  1248 + 64 o + j: of x >= curve_abs[j]
+ *   2208 + 256 o + i: u64 np.histogram(organ_suv, bins)[0][i], edges np.linspace(lo, hi, bins + 1)
+ * Sums are merged from per-block partials in a fixed order (no float atomics): two calls give the same bits.
+ * ws: mmseg_suv_ws_bytes(V) bytes, 256-byte aligned. */
+int mmseg_suv_record_cells(void);
+long long mmseg_suv_ws_bytes(long long V);
+int mmseg_suv_analyze(const void* suv, int suv_datatype, int suv_swap, int suv_scale, double suv_slope,
+                      double suv_inter, const void* seg, int seg_datatype, int seg_swap, int seg_scale,
+                      double seg_slope, double seg_inter, int X, int Y, int Z, int organ_max, int liver_label,
+                      double abs_thr, double pct_thr, double tumor_thr, const double* curve_rel,
+                      const double* curve_abs, int ncurve, int bins, unsigned char* masks, void* record, void* ws,
+                      long long ws_bytes, void* stream);
 /* AdamW step over flat fp32 buffers (torch.optim.AdamW op order, trainer.py:115-117).
  * skip (nullable): one device float, the step's count of out-of-range labels (mmseg_loss_fwd's last workspace
  * float, summed over the ranks under DP); when it is non-zero the kernel leaves p, m and v untouched, so a batch

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Entry point mirroring the reference's `main.py --mode train|eval|inference` (main.py:41-409, 501-549)
-on the MI355X engine.  Other modes (preprocess, analysis) are outside the engine's scope and exit
-with a message.
+"""Entry point mirroring the reference's `main.py --mode train|eval|inference|analysis` (main.py:41-409,
+456-549) on the MI355X engine.  --mode preprocess is outside the engine's scope and exits with a message.
 
     python main.py --mode train --config configs/c2_unet_96_bf16.yaml
     python main.py --mode inference --config configs/c6_unet_nifti.yaml --checkpoint outputs/c6_unet_nifti/best.pth \
         --input data/new_cases --output outputs/predictions
     python main.py --mode inference ... --blend gaussian --tta-flips 0 1 2     (Gaussian blending, 8 mirrored passes)
+    python main.py --mode analysis --config configs/c6_unet_nifti.yaml --input outputs/predictions \
+        --output outputs/analysis                      (SUV statistics, TMTV / TLG, SUV histograms of one case)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode train \
         --config configs/c3_dual_encoder_96_dp.yaml
 """
@@ -49,6 +50,11 @@ def parse_args(argv=None):
     p.add_argument("--tta-flips", nargs="*", type=int, default=None, choices=[0, 1, 2],
                    help="inference: axes (0, 1, 2 = D, H, W of the volume) mirrored for test-time augmentation "
                         "(inference.tta_flips)")
+    p.add_argument("--suv-analysis", action="store_true", help="analysis: run the SUV analysis (analysis.suv.enabled)")
+    p.add_argument("--tmtv-analysis", action="store_true",
+                   help="analysis: run the TMTV analysis (analysis.tmtv.enabled)")
+    p.add_argument("--histogram", action="store_true",
+                   help="analysis: compute the SUV histograms (analysis.histogram.enabled)")
     p.add_argument("--verbose", "-v", action="store_true")
     p.add_argument("--debug", action="store_true")
     return p.parse_args(argv)
@@ -83,6 +89,9 @@ def merge_config_with_args(config, args):
         config.setdefault("inference", {}).setdefault("sliding_window", {})["blend"] = args.blend
     if args.tta_flips is not None:
         config.setdefault("inference", {})["tta_flips"] = list(args.tta_flips)
+    for flag, name in ((args.suv_analysis, "suv"), (args.tmtv_analysis, "tmtv"), (args.histogram, "histogram")):
+        if flag:                                   # reference main.py:280-285
+            config.setdefault("analysis", {}).setdefault(name, {})["enabled"] = True
     config["_args"] = {"mode": args.mode, "input": args.input, "output": args.output, "checkpoint": args.checkpoint,
                        "resume": args.resume, "verbose": args.verbose, "debug": args.debug}
     return config
@@ -132,6 +141,12 @@ def run_inference(config, logger):
     Trainer(config=config, model=model, logger=logger).predict(input_path=input_path, output_path=output_path)
 
 
+def run_analysis(config, logger):
+    """reference main.py:456-498: SUV, TMTV and histogram statistics of the case in --input (analysis/)."""
+    from mmseg_amd.analysis import run_analysis as run
+    return run(config, logger)
+
+
 def main(argv=None):
     args = parse_args(argv)
     config = merge_config_with_args(load_config(args.config), args)
@@ -152,6 +167,8 @@ def main(argv=None):
     elif args.mode == "inference":
         run_inference(config, logger)
         logger.info("Inference completed")
+    elif args.mode == "analysis":
+        run_analysis(config, logger)
     else:
         logger.error(f"--mode {args.mode} is outside the MI355X engine's scope (DESIGN.md 'Out of scope')")
         sys.exit(2)

@@ -15,51 +15,14 @@
 // through LDS (rows padded by one element): the global loads run along the source's
 // fastest axis and the stores along the destination's, both as whole rows of a wave.
 #include "mmseg_common.h"
+#include "nifti_src.h"
 
 namespace {
 
+using namespace nifti_src;     // Src<>, ld16 / ld32, scl, known_datatype
+
 constexpr int NT = 64;            // tile edge = wave width
 constexpr int NW = 4;             // waves per block: wave w moves tile rows w, w + 4, ...
-
-// ---- one source element as a double
-template <int DT> struct Src;
-template <> struct Src<2> {       // uint8
-  static __device__ __forceinline__ double get(const void* p, size_t i, int) { return (double)((const uint8_t*)p)[i]; }
-};
-template <> struct Src<256> {     // int8
-  static __device__ __forceinline__ double get(const void* p, size_t i, int) { return (double)((const int8_t*)p)[i]; }
-};
-__device__ __forceinline__ uint16_t ld16(const void* p, size_t i, int swap) {
-  const uint16_t u = ((const uint16_t*)p)[i];
-  return swap ? __builtin_bswap16(u) : u;
-}
-__device__ __forceinline__ uint32_t ld32(const void* p, size_t i, int swap) {
-  const uint32_t u = ((const uint32_t*)p)[i];
-  return swap ? __builtin_bswap32(u) : u;
-}
-template <> struct Src<4> {       // int16
-  static __device__ __forceinline__ double get(const void* p, size_t i, int s) { return (double)(int16_t)ld16(p, i, s); }
-};
-template <> struct Src<512> {     // uint16
-  static __device__ __forceinline__ double get(const void* p, size_t i, int s) { return (double)ld16(p, i, s); }
-};
-template <> struct Src<8> {       // int32
-  static __device__ __forceinline__ double get(const void* p, size_t i, int s) { return (double)(int32_t)ld32(p, i, s); }
-};
-template <> struct Src<768> {     // uint32
-  static __device__ __forceinline__ double get(const void* p, size_t i, int s) { return (double)ld32(p, i, s); }
-};
-template <> struct Src<16> {      // float32
-  static __device__ __forceinline__ double get(const void* p, size_t i, int s) {
-    return (double)__uint_as_float(ld32(p, i, s));
-  }
-};
-template <> struct Src<64> {      // float64
-  static __device__ __forceinline__ double get(const void* p, size_t i, int s) {
-    const unsigned long long u = ((const unsigned long long*)p)[i];
-    return __longlong_as_double((long long)(s ? __builtin_bswap64(u) : u));
-  }
-};
 
 // ---- the decoded double as the output type; the LDS tile holds at least a dword per element
 template <typename O> struct Dst;
@@ -83,15 +46,6 @@ __device__ __forceinline__ void tile_of_block(int nfast, int nslow, int& tfast, 
   b /= (unsigned)nfast;
   tslow = (int)(b % (unsigned)nslow);
   y = (int)(b / (unsigned)nslow);
-}
-
-// raw * slope, then + inter, each rounded on its own (get_fdata's two numpy operations).  The contraction is
-// switched off here: hipcc contracts by default and __dmul_rn / __dadd_rn are plain * and + to it, so without
-// the pragma the pair becomes one v_fma_f64 and sums that sit on a float32 rounding boundary come out different.
-__device__ __forceinline__ double scl(double v, double slope, double inter) {
-#pragma clang fp contract(off)
-  const double p = v * slope;
-  return p + inter;
 }
 
 template <int DT, typename O>
@@ -161,10 +115,6 @@ __global__ __launch_bounds__(NT * NW) void argmax_encode_kernel(const float* __r
   }
 }
 
-bool known_datatype(int dt) {
-  return dt == 2 || dt == 4 || dt == 8 || dt == 16 || dt == 64 || dt == 256 || dt == 512 || dt == 768;
-}
-
 // blocks of a launch over the 64 x 64 tiles of every y; 0 when they do not fit a 1-D grid
 long long tile_blocks(int X, int Y, int Z) {
   const long long n = (long long)ceil_div(X, NT) * ceil_div(Z, NT) * Y;
@@ -203,7 +153,7 @@ int check_decode_args(const char* what, const void* raw, int datatype, int swap,
   MMSEG_REQUIRE(swap == 0 || swap == 1, "%s: swap is 0 or 1 (got %d)", what, swap);
   MMSEG_REQUIRE(X >= 1 && Y >= 1 && Z >= 1, "%s: empty volume %d x %d x %d", what, X, Y, Z);
   MMSEG_REQUIRE(tile_blocks(X, Y, Z) > 0, "%s: volume %d x %d x %d has too many tiles for one launch", what, X, Y, Z);
-  const int es = datatype == 2 || datatype == 256 ? 1 : datatype == 4 || datatype == 512 ? 2 : datatype == 64 ? 8 : 4;
+  const int es = datatype_bytes(datatype);
   MMSEG_REQUIRE(((uintptr_t)raw & (uintptr_t)(es - 1)) == 0, "%s: raw must be aligned to its %d-byte elements", what, es);
   return 0;
 }
