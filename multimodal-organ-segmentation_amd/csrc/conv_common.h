@@ -1,6 +1,7 @@
-// Shared by the conv sources (conv_gemm.hip and the sources split off it: conv_brick6.hip, conv_brick8.hip,
-// wgrad_reduce.hip): the argument structs and the kernel choice that go from the choosers and entry points to the
-// kernel families, the device helpers more than one source uses, and the host functions that cross sources.
+// Shared by the conv sources (conv_gemm.hip and the sources split off it: conv_brick2.hip, conv_brick6.hip,
+// conv_brick8.hip, conv_brickr.hip, conv_wgrad.hip, wgrad_reduce.hip): the argument structs and the kernel choice that
+// go from the choosers and entry points to the kernel families, the constants and device helpers more than one source
+// uses, and the host functions that cross sources.
 //
 // The types sit in an anonymous namespace: a kernel's symbol carries the name of its argument struct
 // ((anonymous namespace)::GemmArgs ...), and tools/rocprof_families.py, the recorded profiles and the name pins of
@@ -11,9 +12,43 @@
 #pragma once
 #include "mmseg_common.h"
 
+#include <stdlib.h>
+
 #define MMSEG_LOCAL extern "C" __attribute__((visibility("hidden")))
 
 namespace {
+
+// Tuning knobs for in-process A/B runs (tools/kbench.py); defaults are the shipped choice.
+int knob(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
+enum GatherMode { MODE_CONV3 = 0, MODE_POINT = 1, MODE_CONVT_FWD = 2, MODE_CONVT_DGRAD = 3 };
+
+// the 4 x 4 x 8 brick and its halo (conv3_brick_kernel, the brick weight gradients), 32 input channels per chunk
+constexpr int BRK_Z = 4, BRK_Y = 4, BRK_X = 8;
+constexpr int HLO_Z = BRK_Z + 2, HLO_Y = BRK_Y + 2, HLO_X = BRK_X + 2;
+constexpr int HLO_V = HLO_Z * HLO_Y * HLO_X;   // 360 halo voxels
+constexpr int CK = 32;                          // input channels per chunk
+
+// the (4 ZW) x 8 x 8 brick's y / x sides and the LDS halo image of conv3_brick2_kernel and its successors, which
+// the runtime-brick kernel shares
+constexpr int B2_Y = 8, B2_X = 8;
+constexpr int H2_Y = B2_Y + 2, H2_X = B2_X + 2;
+
+template <typename T>
+struct Brick2Layout {
+  static constexpr int QV = 2 * (int)sizeof(T);      // 16-B quads per voxel (32 channels): 4 bf16, 8 f32
+  static constexpr int QG = QV / 4;                    // quads per 8-channel group
+  static constexpr int RY = H2_X * QV + 2;             // quads per halo y-row (padded)
+  static constexpr int RZ = H2_Y * RY;                 // quads per halo z-plane
+};
+
+// conv3_brickr_kernel's limits, which choose_gemm plans a brick within
+constexpr int BR_MAXHV = 640;   // halo voxels staged per block (host guarantees)
+// halo image quads available (host guarantees (bz+2)(by+2)((bx+2)*QV+2) <= this): 40 KB bf16 / 80 KB f32
+__host__ __device__ constexpr int br_xq(int tsize) { return tsize == 2 ? 2560 : 5120; }
 
 // Block timeline probe (diagnostics, built only with -DMMSEG_TIMING_PROBES; tools/convbench.py --probe).
 // Per block b < PROBE_NB: [realtime start, realtime end, memtime start, memtime end, HW_ID, XCC_ID, -, -];
@@ -42,8 +77,8 @@ __device__ __forceinline__ void probe_stamp(int& k) {
 #define PROBE_BLOCK(e) probe_block(e)
 #define PROBE_T() probe_stamp(probe_k)
 #define PROBE_DECL() int probe_k = 0
-// There is no relocatable device code, so every source with probe points has its own g_probe; a source split off
-// conv_gemm.hip defines its setter with this, and mmseg_probe_set (conv_gemm.hip) calls them all.
+// There is no relocatable device code, so every source with probe points has its own g_probe and defines its setter
+// with this; mmseg_probe_set (conv_gemm.hip) calls them all.
 #define MMSEG_PROBE_SETTER(NAME)                                                            \
   MMSEG_LOCAL int NAME(long long* buf) {                                                    \
     return hipMemcpyToSymbol(HIP_SYMBOL(g_probe), &buf, sizeof(buf)) == hipSuccess ? 0 : 1; \
@@ -223,7 +258,10 @@ struct GemmChoice {
   int ksplit;          // the launch's split count (GK_BRICKR: clamped to whole chunk ranges)
   bool reduce;         // a split-K reduce follows
   int ks_want;         // CONV3: the split count this shape wants (mmseg_conv3_splits)
+  int tsize;           // element bytes (2: bf16, 4: fp32): the element type of the instantiation a launcher takes
 };
+// The planning queries' flags: what the launch would carry (mmseg_conv3_kernel / mmseg_conv3_wgrad_kernel).
+enum ChoiceFlags { CF_NORM = 1, CF_INPART = 2, CF_FP8 = 4, CF_GROUPS = 8, CF_PAD16 = 16 };
 
 // part[ks][row][col] -> torch-layout gradient (fixed-order sum over ks).
 //   CONV3 : grad[co][ci][tap]    row=co, col = tap*Cin_pad + ci, ci < Cin_real
@@ -252,9 +290,12 @@ struct WReduceArgs {
 
 // ---- per-family launchers: each maps a GemmChoice to the template instantiation next to its kernels and launches it
 // on the grid the choice carries; launch_gemm (conv_gemm.hip) chooses, checks, calls one and checks the launch
+MMSEG_LOCAL void launch_brickr(const GemmArgs& g, const GemmChoice& c, hipStream_t s);   // GK_BRICKR
+MMSEG_LOCAL void launch_brick2(const GemmArgs& g, const GemmChoice& c, hipStream_t s);   // GK_BRICK2_BN48 / 2 / 3 / 4 / 1
 MMSEG_LOCAL void launch_brick6(const GemmArgs& g, const GemmChoice& c, hipStream_t s);
 MMSEG_LOCAL void launch_brick8(const GemmArgs& g, const GemmChoice& c, hipStream_t s);
 #ifdef MMSEG_TIMING_PROBES
+MMSEG_LOCAL int probe_set_brick2(long long* buf);
 MMSEG_LOCAL int probe_set_brick6(long long* buf);
 MMSEG_LOCAL int probe_set_brick8(long long* buf);
 #endif

@@ -1,7 +1,7 @@
 """Which kernel every 3^3 conv launch takes, checked without a GPU.
 
-The library decides the kernel of a conv forward / data gradient in choose_gemm and of a weight gradient in
-choose_conv3_wgrad (csrc/conv_gemm.hip); the planning queries and the name queries mmseg_conv3_kernel /
+The library decides the kernel of a conv forward / data gradient in choose_gemm (csrc/conv_gemm.hip) and of a weight
+gradient in choose_conv3_wgrad (csrc/conv_wgrad.hip); the planning queries and the name queries mmseg_conv3_kernel /
 mmseg_conv3_wgrad_kernel are thin wrappers over them.  This file sweeps the queries for consistency and pins the
 kernel and split count of the workloads' layers, so a routing change shows up here rather than rounds later as a
 drift of a held-out metric ("The round-5 drift, named")."""

@@ -64,7 +64,7 @@ def family(name: str) -> str:
         return f"conv3_brick_kernel<BN{m.group(1)}>[{dt}]"
     m = re.search(r"conv_gemm_kernelI(?:DF16b|f)Li(\d)ELi(\d)ELi(\d)ELi(\d)ELi(\d)E", name)
     if m:
-        # (WM, WN, TM, TN) template arguments -> the tile name mmseg_last_kernel() reports (conv_gemm.hip)
+        # (WM, WN, TM, TN) template arguments -> the tile name mmseg_last_kernel() reports (choose_gemm, conv_gemm.hip)
         tile = _GEMM_TILES.get(m.group(2, 3, 4, 5), "128x64")
         return f"conv_gemm_kernel<{_MODES[m.group(1)]},{tile}>[{dt}]"
     # brick6 / brick8 under the timer's family names (engine/profiler.py: mmseg_last_kernel()), so a family
