@@ -120,6 +120,12 @@ int mmseg_stem_fwd(const void* x, int ldx, int cr, const float* w, const float* 
                    int H, int W, int Co, int dtype, void* stream);
 int mmseg_stem_wgrad(const void* dy, int lddy, const void* x, int ldx, int cr, float* part, float* bias_part, int N,
                      int D, int H, int W, int Co, int ksplit, int dtype, void* stream);
+/* Data gradient of the first conv, for the attribution paths (explainability): g is the conv's output gradient
+ * (NDHWC, Co channels, a multiple of 8, pitch ldg, engine dtype), w the fp32 weight [Co][Ci][3][3][3] with Ci <= 8;
+ * writes fp32 dx [N][Cx][D][H][W] (NCDHW) channels [c0, c0 + Ci), summed into when accumulate.  Any D, H, W; zero
+ * padding as the forward.  g is staged through an LDS halo tile, so it is read from HBM once. */
+int mmseg_stem_dgrad(const void* g, int ldg, int Co, const float* w, int Ci, float* dx, int Cx, int c0, int N, int D,
+                     int H, int W, int accumulate, int dtype, void* stream);
 /* mmseg_stem_wgrad whose dy is the gradient of an InstanceNorm + ReLU OUTPUT: the norm's backward (pre-norm
  * input inx with pitch ldinx, statistics inmean / inrstd [N][Co], coefficients incoef [N][Co][2] from
  * mmseg_instnorm_bwd_coef) is applied while staging dy -- the values mmseg_instnorm_bwd would write, bit for bit --
@@ -575,6 +581,7 @@ int mmseg_head_bwd(const void* x, int ldx, int Cin, const float* W, const float*
 int mmseg_head_bwd_zw(const void* x, int ldx, int Cin, const float* W, const float* dscale, int C, int N, long long V,
                       const float* dlogits, void* dx, int lddx, int zcols, float* gW, float* gb, float* ws,
                       int accumulate, int dtype, void* stream);
+/* (gW null: the data gradient alone -- no weight / bias gradient launch; ws is then unused.) */
 /* Fused softmax + Dice/Tversky + CE statistics and loss (losses.py:39-80, 160-185,
  * 216-228).  type 0: dice_w*Dice + ce_w*CE ; type 1: dice_w*Tversky + ce_w*CE ; type 2: FocalLoss
  * (losses.py:83-125: mean of (1 - exp(-ce_i))^gamma * ce_i with ce_i the class-weighted voxel CE; gamma is
@@ -716,6 +723,39 @@ int mmseg_adamw_pack(float* p, const float* g, float* m, float* v, const void* d
                      void* stream);
 int mmseg_adamw_pack_dev(float* p, const float* g, float* m, float* v, const void* descs, int n, int nblocks,
                          const float* hyper, const float* skip, int dtype, void* stream);
+
+/* ------------------------------------------------------- explainability */
+/* Grad-CAM / Grad-CAM++ / gradient attributions (reference src/explainability/gradcam.py, shap_analysis.py) over
+ * the engine's tapped activations and gradient sources.  Fixed-order reductions, no float atomics, no allocation.
+ * mmseg_explain_ws_floats(): floats of the ws of mmseg_explain_seed and mmseg_cam_upsample_norm. */
+long long mmseg_explain_ws_floats(void);
+/* Seed gradient of a class score: logits [1][C][V] fp32 -> dlogits [1][C][V].  mode 0: d logits[0, cls].max()
+ * (1 / k on each of the k maxima, as torch's amax backward); mode 1: d logits[0, cls].mean() = 1 / V.  Zero on every
+ * other channel. */
+int mmseg_explain_seed(const float* logits, int C, long long V, int cls, int mode, float* dlogits, float* ws,
+                       void* stream);
+/* Per-channel CAM weights [C] of one sample from its activation act [V][C] (pitch lda, engine dtype) and the
+ * sources of its output gradient g = scale1 * p1 + maxpool_bwd(pool_dy, pool_idx), gathered as
+ * mmseg_instnorm_relu_bwd gathers them (either source may be null, not both).  mode 0 (Grad-CAM): mean_v g (act
+ * unused).  mode 1 (Grad-CAM++): sum_v alpha g over g > 0, alpha = g^2 / (2 g^2 + (sum_v act) g^3 + 1e-8); voxels
+ * with g <= 0 contribute exactly 0.  fp32 sums.  ws: mmseg_cam_ws_floats(V, C) floats. */
+long long mmseg_cam_ws_floats(long long V, int C);
+int mmseg_cam_weights(const void* act, int lda, const void* p1, int ld1, float scale1, const void* pool_dy, int pool_ld,
+                      const uint8_t* pool_idx, int D, int H, int W, int C, int mode, float* weights, float* ws,
+                      int dtype, void* stream);
+/* cam[v] = relu(sum_c weights[c] * act[v][c]), fp32 [V]. */
+int mmseg_cam_combine(const void* act, int lda, const float* weights, long long V, int C, float* cam, int dtype,
+                      void* stream);
+/* F.interpolate(cam [d][h][w], size (D, H, W), mode trilinear, align_corners False) -- scale 1, 2, 4, 8 or 16 per
+ * axis -- then (x - min) / (max - min + 1e-8) over the result, fp32 [D][H][W] (the input's own axis order, the
+ * reference's [H, W, D]).  Two launches.  ws: mmseg_explain_ws_floats() floats. */
+int mmseg_cam_upsample_norm(const float* cam, int d, int h, int w, float* out, int D, int H, int W, float* ws,
+                            void* stream);
+/* out = baseline + t (x - baseline) (integrated-gradients path point) and out = (x - baseline) * grad * scale
+ * (the attribution); baseline null: zeros.  Contiguous fp32, n elements. */
+int mmseg_attr_lerp(const float* x, const float* baseline, float t, float* out, long long n, void* stream);
+int mmseg_attr_finish(const float* x, const float* baseline, const float* grad, float scale, float* out, long long n,
+                      void* stream);
 
 #ifdef __cplusplus
 }

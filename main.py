@@ -6,6 +6,8 @@
     python main.py --mode inference --config configs/c6_unet_nifti.yaml --checkpoint outputs/c6_unet_nifti/best.pth \
         --input data/new_cases --output outputs/predictions
     python main.py --mode inference ... --blend gaussian --tta-flips 0 1 2     (Gaussian blending, 8 mirrored passes)
+    python main.py --mode eval --config configs/c6_unet_nifti.yaml --checkpoint outputs/c6_unet_nifti/best.pth \
+        --gradcam --shap                               (Grad-CAM heat maps and gradient attributions, explain/)
     python main.py --mode analysis --config configs/c6_unet_nifti.yaml --input outputs/predictions \
         --output outputs/analysis                      (SUV statistics, TMTV / TLG, SUV histograms of one case)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode train \
@@ -55,6 +57,10 @@ def parse_args(argv=None):
                    help="analysis: run the TMTV analysis (analysis.tmtv.enabled)")
     p.add_argument("--histogram", action="store_true",
                    help="analysis: compute the SUV histograms (analysis.histogram.enabled)")
+    p.add_argument("--gradcam", action="store_true",
+                   help="eval: write Grad-CAM heat maps of the first validation cases (explainability.gradcam.enabled)")
+    p.add_argument("--shap", action="store_true",
+                   help="eval: write gradient attributions of the first validation cases (explainability.shap.enabled)")
     p.add_argument("--verbose", "-v", action="store_true")
     p.add_argument("--debug", action="store_true")
     return p.parse_args(argv)
@@ -92,6 +98,9 @@ def merge_config_with_args(config, args):
     for flag, name in ((args.suv_analysis, "suv"), (args.tmtv_analysis, "tmtv"), (args.histogram, "histogram")):
         if flag:                                   # reference main.py:280-285
             config.setdefault("analysis", {}).setdefault(name, {})["enabled"] = True
+    for flag, name in ((args.gradcam, "gradcam"), (args.shap, "shap")):
+        if flag:                                   # reference main.py --gradcam
+            config.setdefault("explainability", {}).setdefault(name, {})["enabled"] = True
     config["_args"] = {"mode": args.mode, "input": args.input, "output": args.output, "checkpoint": args.checkpoint,
                        "resume": args.resume, "verbose": args.verbose, "debug": args.debug}
     return config
@@ -123,6 +132,11 @@ def run_eval(config, logger):
                     f"recall: {metrics['recall']:.4f} F1: {metrics['f1']:.4f}")
         logger.info(f"Precision per class: {metrics['precision_per_class']} recall per class: "
                     f"{metrics['recall_per_class']}")
+    from mmseg_amd.explainability import explain_config, run_explain
+    ex = explain_config(config)
+    if (ex["gradcam"]["enabled"] or ex["shap"]["enabled"]) and ddp.rank() == 0:
+        files = run_explain(config, model, get_dataloader(config, split=split), logger)
+        logger.info(f"Explainability: {len(files)} heat-map files written")
     return metrics
 
 

@@ -1537,8 +1537,9 @@ int mmseg_head_bwd_zw(const void* x, int ldx, int Cin, const float* W, const flo
   const size_t shm2 = 0;
   // weight-gradient partials first: dx may alias x (the engine reuses the feature buffer)
   if (dtype == MMSEG_BF16) {
-    MMSEG_LAUNCH(head_wgrad_partial<bf16_t>, dim3((int)nblk), dim3(256), shm2, s, (const bf16_t*)x, ldx, dlogits,
-                       dscale, C, Cin, V, N, vpc, ws);
+    if (gW)
+      MMSEG_LAUNCH(head_wgrad_partial<bf16_t>, dim3((int)nblk), dim3(256), shm2, s, (const bf16_t*)x, ldx, dlogits,
+                   dscale, C, Cin, V, N, vpc, ws);
     if (dx && C <= 8)
       MMSEG_LAUNCH((head_dgrad_g_kernel<bf16_t, 8>), dim3(qgrid), dim3(256), 0, s, dlogits, W, dscale, C, Cin, V, N,
                    (bf16_t*)dx, lddx, zcols / 8);
@@ -1546,8 +1547,9 @@ int mmseg_head_bwd_zw(const void* x, int ldx, int Cin, const float* W, const flo
       MMSEG_LAUNCH((head_dgrad_g_kernel<bf16_t, CMAX>), dim3(qgrid), dim3(256), 0, s, dlogits, W, dscale, C, Cin, V,
                    N, (bf16_t*)dx, lddx, zcols / 8);
   } else {
-    MMSEG_LAUNCH(head_wgrad_partial<float>, dim3((int)nblk), dim3(256), shm2, s, (const float*)x, ldx, dlogits,
-                       dscale, C, Cin, V, N, vpc, ws);
+    if (gW)
+      MMSEG_LAUNCH(head_wgrad_partial<float>, dim3((int)nblk), dim3(256), shm2, s, (const float*)x, ldx, dlogits,
+                   dscale, C, Cin, V, N, vpc, ws);
     if (dx && C <= 8)
       MMSEG_LAUNCH((head_dgrad_g_kernel<float, 8>), dim3(qgrid), dim3(256), 0, s, dlogits, W, dscale, C, Cin, V, N,
                    (float*)dx, lddx, zcols / 8);
@@ -1556,6 +1558,7 @@ int mmseg_head_bwd_zw(const void* x, int ldx, int Cin, const float* W, const flo
                    N, (float*)dx, lddx, zcols / 8);
   }
   if (mmseg::check_launch("head_bwd")) return 1;
+  if (!gW) return 0;   // data gradient only (explainability): no weight / bias gradient, no reduce
   MMSEG_LAUNCH(head_wgrad_reduce, dim3(ceil_div(C * Cin + C, 4)), dim3(256), 0, s, ws, (int)nblk, C, Cin, gW,
                      gb, accumulate);
   return mmseg::check_launch("head_wgrad_reduce");

@@ -325,6 +325,82 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CR == 1 ? 4
 
 int stem_kp(int cr) { return ((27 * cr + 31) / 32) * 32; }
 
+// --------------------------------------------------------- input gradient
+// dx[n][c0 + ci][u] = sum_co sum_t g[n][u - delta_t][co] * w[co][ci][t]: the first conv's data gradient for the
+// attribution paths (explainability), fp32 straight into the NCDHW input gradient at a channel offset.  A block
+// owns a 4x4x16 output brick (one voxel per thread, 16 consecutive x per row of the NCDHW store) and stages the
+// brick's 6x6x18 halo of g through LDS, CC channels per pass, so g is read from HBM once (plus the halo overlap);
+// the taps are applied flipped (halo voxel u + 1 - delta_t), zero outside the volume as the forward pads.
+constexpr int GZ = 4, GY = 4, GX = 16;
+constexpr int GHZ = GZ + 2, GHY = GY + 2, GHX = GX + 2;
+constexpr int GHV = GHZ * GHY * GHX;   // 648 halo voxels
+
+template <typename T, int CC, int CIT>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const T* __restrict__ g, int ldg, int Co,
+                                                         const float* __restrict__ w, int Ci, float* __restrict__ dx,
+                                                         int Cx, int c0, int D, int H, int W, int accumulate) {
+  __shared__ __attribute__((aligned(16))) T Gl[GHV * CC];
+  __shared__ float Wl[27 * CIT * CC];
+  const int tid = threadIdx.x;
+  const int bz_n = (D + GZ - 1) / GZ, by_n = (H + GY - 1) / GY, bx_n = (W + GX - 1) / GX;
+  int b = blockIdx.x;
+  const int bx = b % bx_n; b /= bx_n;
+  const int by = b % by_n; b /= by_n;
+  const int bz = b % bz_n;
+  const int n = b / bz_n;
+  const long long HW = (long long)H * W;
+  const long long nbase = (long long)n * D * HW;
+  const int z0 = bz * GZ, y0 = by * GY, x0 = bx * GX;
+  const int lx = tid % GX, ly = (tid / GX) % GY, lz = tid / (GX * GY);
+  float acc[CIT];
+#pragma unroll
+  for (int ci = 0; ci < CIT; ++ci) acc[ci] = 0.f;
+  constexpr int P = CC / 8;
+  for (int cb = 0; cb < Co; cb += CC) {
+    __syncthreads();   // the previous pass's reads
+    for (int e = tid; e < GHV * P; e += 256) {
+      const int hv = e / P, p = e - hv * P;
+      const int hx = hv % GHX, hy = (hv / GHX) % GHY, hz = hv / (GHX * GHY);
+      const int z = z0 - 1 + hz, y = y0 - 1 + hy, x = x0 - 1 + hx;
+      V8<T> v;
+      if ((unsigned)z < (unsigned)D && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W)
+        v.load(g + (nbase + z * HW + (long long)y * W + x) * ldg + cb + p * 8);
+      else
+        v.zero();
+      v.store(Gl + hv * CC + p * 8);
+    }
+    for (int e = tid; e < 27 * CIT * CC; e += 256) {
+      const int t = e / (CIT * CC), r = e - t * (CIT * CC);
+      const int ci = r / CC, c = r - ci * CC;
+      Wl[e] = ci < Ci ? w[((long long)(cb + c) * Ci + ci) * 27 + t] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 3
+    for (int t = 0; t < 27; ++t) {
+      const int kz = t / 9, ky = (t / 3) % 3, kx = t % 3;
+      const int hv = ((lz + 2 - kz) * GHY + (ly + 2 - ky)) * GHX + (lx + 2 - kx);
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        V8<T> v;
+        v.load(Gl + hv * CC + p * 8);
+#pragma unroll
+        for (int ci = 0; ci < CIT; ++ci)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[ci] = fmaf(v.get(j), Wl[(t * CIT + ci) * CC + p * 8 + j], acc[ci]);
+      }
+    }
+  }
+  const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+  if (z < D && y < H && x < W) {
+#pragma unroll
+    for (int ci = 0; ci < CIT; ++ci) {
+      if (ci >= Ci) break;
+      float* o = dx + ((long long)n * Cx + c0 + ci) * D * HW + z * HW + (long long)y * W + x;
+      *o = accumulate ? *o + acc[ci] : acc[ci];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -432,6 +508,44 @@ int mmseg_stem_wgrad_inb(const void* dy, int lddy, const void* x, int ldx, int c
     else run(float{}, std::integral_constant<int, 2>{});
   }
   return mmseg::check_launch("stem_wgrad");
+}
+
+// Data gradient of the first conv (explainability: gradient-SHAP, integrated gradients): g = the conv's output
+// gradient, NDHWC with Co channels (a multiple of 8) at pitch ldg, in the engine dtype; w the fp32 weight
+// [Co][Ci][3][3][3], Ci <= 8; dx fp32 NCDHW [N][Cx][D][H][W], channels [c0, c0 + Ci) written (accumulate: summed
+// into).  Any D, H, W; zero padding at the borders as the forward.
+int mmseg_stem_dgrad(const void* g, int ldg, int Co, const float* w, int Ci, float* dx, int Cx, int c0, int N, int D,
+                     int H, int W, int accumulate, int dtype, void* stream) {
+  MMSEG_REQUIRE(g && w && dx, "stem_dgrad: null pointer");
+  MMSEG_REQUIRE(Co >= 8 && Co % 8 == 0 && ldg >= Co && ldg % 8 == 0, "stem_dgrad: Co %d ldg %d", Co, ldg);
+  MMSEG_REQUIRE(Ci >= 1 && Ci <= 8 && c0 >= 0 && c0 + Ci <= Cx, "stem_dgrad: channels [%d, %d) of %d (Ci <= 8)", c0,
+                c0 + Ci, Cx);
+  MMSEG_REQUIRE(N >= 1 && D >= 1 && H >= 1 && W >= 1, "stem_dgrad: shape");
+  const long long nb = (long long)N * ((D + GZ - 1) / GZ) * ((H + GY - 1) / GY) * ((W + GX - 1) / GX);
+  MMSEG_REQUIRE(nb < (1LL << 31), "stem_dgrad: grid");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)nb), blk(256);
+  mmseg::note_kernel("stem_dgrad_kernel");
+  auto run = [&](auto tag, auto cc) {
+    using T = decltype(tag);
+    constexpr int CC = decltype(cc)::value;
+    const T* G = reinterpret_cast<const T*>(g);
+#define STEM_DGRAD_LAUNCH(CIT) \
+  MMSEG_LAUNCH((stem_dgrad_kernel<T, CC, CIT>), grid, blk, 0, s, G, ldg, Co, w, Ci, dx, Cx, c0, D, H, W, accumulate)
+    if (Ci == 1) STEM_DGRAD_LAUNCH(1);
+    else if (Ci == 2) STEM_DGRAD_LAUNCH(2);
+    else if (Ci <= 4) STEM_DGRAD_LAUNCH(4);
+    else STEM_DGRAD_LAUNCH(8);
+#undef STEM_DGRAD_LAUNCH
+  };
+  if (dtype == MMSEG_BF16) {
+    if (Co % 16 == 0) run(bf16_t{}, std::integral_constant<int, 16>{});
+    else run(bf16_t{}, std::integral_constant<int, 8>{});
+  } else {
+    if (Co % 16 == 0) run(float{}, std::integral_constant<int, 16>{});
+    else run(float{}, std::integral_constant<int, 8>{});
+  }
+  return mmseg::check_launch("stem_dgrad");
 }
 
 }  // extern "C"

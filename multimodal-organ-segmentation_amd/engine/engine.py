@@ -60,7 +60,24 @@ class SegEngine:
         self.rt.join_side()
         self.flat.end_backward()
 
-    # ---- fused head + loss (Trainer fast path)
+    # ---- explainability: taps + data-only backward + input gradient
+    def explain(self, x: torch.Tensor, dlogits, taps=(), input_grad: bool = False,
+                dx: Optional[torch.Tensor] = None, accumulate: bool = False):
+        """One eval forward and the data-only backward of the seed gradient `dlogits` (a [1, C, D, H, W] tensor, or
+        a function of the logits that returns it): per name in `taps` the layer's output activation and the sources
+        of its output gradient, plus the input gradient when asked (programs.ExplainResult).  No parameter gradient,
+        packed weight image or optimizer state is touched."""
+        if self.kind == "swin_unetr":
+            raise NotImplementedError("explain: SwinUNETR has no taps / data-only backward on the engine "
+                                      "(UNet3D and DualEncoder do)")
+        if x.dtype != torch.float32:
+            x = x.float()
+        x = x.contiguous()
+        self.ensure(x.device)
+        with torch.no_grad():
+            return self.program.explain(x, dlogits, taps, input_grad, dx, accumulate)
+
+
     def forward_loss(self, x: torch.Tensor, training: bool, labels: torch.Tensor, spec: dict,
                      cw: Optional[torch.Tensor]) -> torch.Tensor:
         if x.dtype != torch.float32:

@@ -406,6 +406,8 @@ class Conv3:
         backward while staging it (mmseg_stem_wgrad_inb)."""
         L, s, code = self.rt.lib, self.rt.stream, self.rt.code
         V = x.N * x.V
+        if self.rt.data_only:      # explainability: no weight / bias gradient, the data gradient alone
+            return self._dgrad(x, dy, dx, inp) if dx is not None else None
         if dx is None and norm is None and (inb is not None or self._stem(x, dy.ld)):
             # 1,024 splits: one round of resident blocks at 96^3 B=2 and half the partials of 2,048 (r02 stembench:
             # 42 + 12.8 us against 44 + 19.7 us with the reduce)
@@ -470,36 +472,42 @@ class Conv3:
         else:
             reduce(s)
         if dx is not None:
-            # dx = (lo, hi): columns [0, lo.C) into lo, the rest into hi (two dense tensors, mmseg_conv_gemm_split)
-            split = isinstance(dx, tuple)
-            d0 = dx[0] if split else dx
-            M = V
-            nc = self.ncols_d
-            ks = L.mmseg_conv3_splits(M, nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, dy.ld, d0.ld, code)
-            ws = self.rt.ws(ks * M * nc) if ks > 1 else None
-            with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Co * 27 * self.Ci,
-                              nbytes=_io_bytes(self.rt, M, self.Co, self.Cip, 27 * self.Cip * self.Co)):
-                nch = 0
-                if inp is not None and not split and ks == 1 and os.environ.get("MMSEG_DGRAD_IN_PART", "1") != "0":
-                    nch = L.mmseg_conv3_dgrad_in_chunks(M, nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W,
-                                                        dy.ld, dx.ld, code)
-                if nch:
-                    xi, im, ir = inp
-                    size = x.N * nch * nc * 2
-                    if getattr(self, "_inpart", None) is None or self._inpart.numel() != size:
-                        self._inpart = torch.empty(size, dtype=torch.float32, device=self.rt.device)
-                    L.mmseg_conv3_dgrad_in(dy.ptr, dy.ld, ptr(self.wd), dx.ptr, dx.ld, M, nc, self.Cpad_d, self.KGd,
-                                           self.dshift, x.D, x.H, x.W, xi.ptr, xi.ld, ptr(im), ptr(ir),
-                                           ptr(self._inpart), code, s)
-                    return self._inpart, nch
-                if split:
-                    L.mmseg_conv_gemm_split(dy.ptr, dy.ld, ptr(self.wd), None, d0.ptr, d0.ld, dx[1].ptr, dx[1].ld,
-                                            d0.C, ptr(ws), MODE_CONV3, M, nc, self.Cpad_d, self.KGd, self.dshift, x.D,
-                                            x.H, x.W, ks, self.kreal_d, code, s)
-                else:
-                    L.mmseg_conv_gemm_zw(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, ptr(ws), MODE_CONV3, M,
-                                         nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, ks, self.kreal_d,
-                                         _zcols(dx, nc), code, s)
+            return self._dgrad(x, dy, dx, inp)
+
+    def _dgrad(self, x: Act, dy: Act, dx, inp: Optional[Tuple[Act, torch.Tensor, torch.Tensor]]):
+        """The data gradient of _bwd (its last launch)."""
+        L, s, code = self.rt.lib, self.rt.stream, self.rt.code
+        V = x.N * x.V
+        # dx = (lo, hi): columns [0, lo.C) into lo, the rest into hi (two dense tensors, mmseg_conv_gemm_split)
+        split = isinstance(dx, tuple)
+        d0 = dx[0] if split else dx
+        M = V
+        nc = self.ncols_d
+        ks = L.mmseg_conv3_splits(M, nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, dy.ld, d0.ld, code)
+        ws = self.rt.ws(ks * M * nc) if ks > 1 else None
+        with TIMER.region(_gemm_name(self.rt), flops=2.0 * M * self.Co * 27 * self.Ci,
+                          nbytes=_io_bytes(self.rt, M, self.Co, self.Cip, 27 * self.Cip * self.Co)):
+            nch = 0
+            if inp is not None and not split and ks == 1 and os.environ.get("MMSEG_DGRAD_IN_PART", "1") != "0":
+                nch = L.mmseg_conv3_dgrad_in_chunks(M, nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W,
+                                                    dy.ld, dx.ld, code)
+            if nch:
+                xi, im, ir = inp
+                size = x.N * nch * nc * 2
+                if getattr(self, "_inpart", None) is None or self._inpart.numel() != size:
+                    self._inpart = torch.empty(size, dtype=torch.float32, device=self.rt.device)
+                L.mmseg_conv3_dgrad_in(dy.ptr, dy.ld, ptr(self.wd), dx.ptr, dx.ld, M, nc, self.Cpad_d, self.KGd,
+                                       self.dshift, x.D, x.H, x.W, xi.ptr, xi.ld, ptr(im), ptr(ir),
+                                       ptr(self._inpart), code, s)
+                return self._inpart, nch
+            if split:
+                L.mmseg_conv_gemm_split(dy.ptr, dy.ld, ptr(self.wd), None, d0.ptr, d0.ld, dx[1].ptr, dx[1].ld,
+                                        d0.C, ptr(ws), MODE_CONV3, M, nc, self.Cpad_d, self.KGd, self.dshift, x.D,
+                                        x.H, x.W, ks, self.kreal_d, code, s)
+            else:
+                L.mmseg_conv_gemm_zw(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, ptr(ws), MODE_CONV3, M,
+                                     nc, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, ks, self.kreal_d,
+                                     _zcols(dx, nc), code, s)
 
 
 class ConvT2:
@@ -548,6 +556,19 @@ class ConvT2:
         """x: input grid (D,H,W); dy: output grid (2D,2H,2W)."""
         L, s, code = self.rt.lib, self.rt.stream, self.rt.code
         V = x.N * x.V
+        if not self.rt.data_only:
+            self._wgrad(x, dy, accumulate)
+        if dx is not None:
+            ks = _gemm_ksplit(V, self.Ci, self.KGd)
+            ws = self.rt.ws(ks * V * self.Ci) if ks > 1 else None
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * 8 * self.Co,
+                              nbytes=_io_bytes(self.rt, V, 8 * self.Co, self.Ci, 8 * self.Ci * self.Co)):
+                L.mmseg_conv_gemm(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, ptr(ws), MODE_CONVT_DGRAD, V,
+                                  self.Ci, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, ks, code, s)
+
+    def _wgrad(self, x: Act, dy: Act, accumulate: bool):
+        L, s, code = self.rt.lib, self.rt.stream, self.rt.code
+        V = x.N * x.V
         ncols = 8 * self.Cop
         ks = L.mmseg_wgrad_splits(V, _wgrad_ksplit(self.Ci, ncols, V))
         # bias gradient: column sums of the gathered dy tile emitted by the weight-gradient kernel itself
@@ -571,13 +592,6 @@ class ConvT2:
             L.mmseg_colsum(dy.ptr, dy.ld, self.Co, dy.N * dy.V, ptr(part), 256, ptr(self.flat.grad(self.up.bias)),
                            int(accumulate), code, s)
         self.flat.mark(*[p for p in (self.up.weight, self.up.bias) if p is not None])
-        if dx is not None:
-            ks = _gemm_ksplit(V, self.Ci, self.KGd)
-            ws = self.rt.ws(ks * V * self.Ci) if ks > 1 else None
-            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * 8 * self.Co,
-                              nbytes=_io_bytes(self.rt, V, 8 * self.Co, self.Ci, 8 * self.Ci * self.Co)):
-                L.mmseg_conv_gemm(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, ptr(ws), MODE_CONVT_DGRAD, V,
-                                  self.Ci, self.Cpad_d, self.KGd, self.dshift, x.D, x.H, x.W, ks, code, s)
 
 
 class Point:
@@ -611,6 +625,17 @@ class Point:
     def bwd(self, x: Act, dy: Act, dx: Optional[Act], accumulate: bool):
         L, s, code = self.rt.lib, self.rt.stream, self.rt.code
         V = x.N * x.V
+        if not self.rt.data_only:
+            self._wgrad(x, dy, accumulate)
+        if dx is not None:
+            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * self.Co,
+                              nbytes=_io_bytes(self.rt, V, self.Co, self.Ci, self.Ci * self.Co)):
+                L.mmseg_conv_gemm(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, None, MODE_POINT, V, self.Ci,
+                                  self.Cpad_d, self.KGd, 0, x.D, x.H, x.W, 1, code, s)
+
+    def _wgrad(self, x: Act, dy: Act, accumulate: bool):
+        L, s, code = self.rt.lib, self.rt.stream, self.rt.code
+        V = x.N * x.V
         ks = L.mmseg_wgrad_splits(V, _wgrad_ksplit(self.Co, self.Ci, V))
         defer = self.rt.defer_wred(self.flat)
         nfl = ks * self.Co * self.Ci + ks * self.Co
@@ -624,11 +649,6 @@ class Point:
             ptr(part), ptr(self.flat.grad(self.conv.weight)), bpart, ptr(self.flat.grad(self.conv.bias)), self.Co,
             self.Ci, ks, self.Ci, self.Ci, 1, int(accumulate), s)
         self.flat.mark(self.conv.weight, self.conv.bias)
-        if dx is not None:
-            with TIMER.region(_gemm_name(self.rt), flops=2.0 * V * self.Ci * self.Co,
-                              nbytes=_io_bytes(self.rt, V, self.Co, self.Ci, self.Ci * self.Co)):
-                L.mmseg_conv_gemm(dy.ptr, dy.ld, ptr(self.wd), None, dx.ptr, dx.ld, None, MODE_POINT, V, self.Ci,
-                                  self.Cpad_d, self.KGd, 0, x.D, x.H, x.W, 1, code, s)
 
 
 class Block:
@@ -746,7 +766,7 @@ class Block:
         else:
             part = self.c2.bwd(self.y1, g2, dy1, accumulate, inp=inp)
         g1 = self.x1
-        if dxin is None and self._stem_inb(xin):
+        if dxin is None and not self.rt.data_only and self._stem_inb(xin):
             # conv1 is the stem and its weight gradient is the only reader of conv1's InstanceNorm input gradient:
             # only the norm's coefficients are formed here, the stem applies the backward while staging dy1
             L, s, code = self.rt.lib, self.rt.stream, self.rt.code
@@ -831,7 +851,7 @@ class ConvGroup:
         wsf = L.mmseg_conv3_wgrad_group_ws_floats(V, c.Co, c.Cip, c.Ci, c.cpg_shift, x.D, x.H, x.W, dy.ld, x.ld,
                                                   self.G, code)
         defer = wsf > 0 and self.rt.defer_wred(self.flat)
-        ws = c._part(wsf, own=defer)
+        ws = c._part(wsf, own=defer) if not self.rt.data_only else None
         gw = ptr(self.flat.grad(c.conv.weight))
         gb = ptr(self.flat.grad(c.conv.bias)) if c.conv.bias is not None else None
         args = (dy.ptr, dy.ld, x.ptr, x.ld, gw, gb, c.Co, c.Cip, c.Ci, c.cpg_shift, V, x.D, x.H, x.W, ptr(ws), wsf,
@@ -846,8 +866,9 @@ class ConvGroup:
                 L.mmseg_conv3_wgrad_group(*args, 6 if defer else 2, code, s2)
             for cc in self.convs:
                 self.flat.mark(*[p for p in (cc.conv.weight, cc.conv.bias) if p is not None])
-        wkernel(self.rt.stream)
-        c._reduce_after(reduce)
+        if not self.rt.data_only:      # (explainability: the data gradient alone)
+            wkernel(self.rt.stream)
+            c._reduce_after(reduce)
         try:
             if dx is None:
                 return
@@ -986,6 +1007,11 @@ class Head:
 
     def bwd(self, x: Act, dlogits: torch.Tensor, dx: Optional[Act], accumulate: bool):
         L = self.rt.lib
+        if self.rt.data_only:          # explainability: d(input) alone, no weight / bias gradient launch
+            L.mmseg_head_bwd_zw(x.ptr, x.ld, self.Cin, ptr(self.conv.weight), ptr(self.dscale), self.C, x.N, x.V,
+                                ptr(dlogits), dx.ptr, dx.ld, dx.wcols, None, None, None, 0, self.rt.code,
+                                self.rt.stream)
+            return
         ws = self.rt.ws(L.mmseg_head_ws_floats(self.C, self.Cin, x.N, x.V))
         L.mmseg_head_bwd_zw(x.ptr, x.ld, self.Cin, ptr(self.conv.weight), ptr(self.dscale), self.C, x.N, x.V,
                             ptr(dlogits), dx.ptr if dx is not None else None, dx.ld if dx is not None else 0,

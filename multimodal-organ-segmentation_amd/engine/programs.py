@@ -15,7 +15,9 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-from typing import Dict, List, Optional, Tuple
+import re
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -27,6 +29,66 @@ from .runtime import Act, FlatParams, Runtime
 
 
 SMALL_IN_V = 4096   # norm_pool.hip knob_small_v(): at or below it InstanceNorm is one launch (stats + apply)
+
+
+@dataclass
+class Tap:
+    """A tapped layer of one explain call (SegEngine.explain): `act` is a copy of the layer's output, [V][C] in the
+    engine dtype; `grad` the sources of the gradient of that output (layers.DySpec: p1 * scale1 plus the max-pool
+    scatter of pool_dy through pool_idx), views of the engine's own buffers -- valid until the engine runs again."""
+    name: str
+    act: torch.Tensor
+    dims: Tuple[int, int, int]
+    C: int
+    grad: DySpec
+
+
+@dataclass
+class ExplainResult:
+    logits: torch.Tensor
+    taps: Dict[str, Tap]
+    dx: Optional[torch.Tensor]      # fp32 [1, Cx, D, H, W] when input_grad
+
+
+Seed = Union[torch.Tensor, Callable[[torch.Tensor], torch.Tensor]]
+
+
+def _snapshot(a: Act) -> torch.Tensor:
+    """Sample 0 of an activation view as a dense [V][C] tensor of its own."""
+    return a.buf[: a.V * a.ld].view(a.V, a.ld)[:, a.off:a.off + a.C].clone(memory_format=torch.contiguous_format)
+
+
+def _unknown_tap(name: str, valid: List[str]) -> ValueError:
+    return ValueError(f"unknown explainability layer {name!r}; valid names (with or without a 'backbone.' prefix): "
+                      + ", ".join(valid))
+
+
+def _explain_input(x: torch.Tensor, dx: Optional[torch.Tensor], input_grad: bool) -> Optional[torch.Tensor]:
+    if x.dim() != 5 or x.shape[0] != 1:
+        raise ValueError(f"explain: one sample per call (input [1, C, D, H, W]), got {tuple(x.shape)}")
+    if not input_grad:
+        return None
+    if dx is None:
+        return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if dx.shape != x.shape or dx.dtype != torch.float32 or not dx.is_contiguous():
+        raise ValueError("explain: dx must be a contiguous float32 tensor of the input's shape")
+    return dx
+
+
+def _seed(dlogits: Seed, logits: torch.Tensor) -> torch.Tensor:
+    if callable(dlogits):
+        dlogits = dlogits(logits)
+    if dlogits.shape != logits.shape:
+        raise ValueError(f"explain: dlogits {tuple(dlogits.shape)} does not match the logits {tuple(logits.shape)}")
+    return dlogits.float().contiguous()
+
+
+def _stem_dgrad(rt: Runtime, block: Block, dx: torch.Tensor, c0: int, accumulate: bool) -> None:
+    """d(input channels [c0, c0 + Ci)) from the gradient of the block's first conv output (in block.x1 once the
+    block's data-only backward has run): mmseg_stem_dgrad, fp32 straight into the NCDHW dx."""
+    g, c1 = block.x1, block.c1
+    rt.lib.mmseg_stem_dgrad(g.ptr, g.ld, c1.Co, ptr(c1.conv.weight), c1.Ci, ptr(dx), dx.shape[1], c0, g.N, g.D, g.H,
+                            g.W, int(accumulate), rt.code, rt.stream)
 
 
 def _check_dims(D, H, W, levels):
@@ -221,6 +283,65 @@ class UNetProgram:
             self.enc[l - 1].bwd(self.pooled[l], dy, self.dpooled[l], accumulate)   # dp aliases pooled (default)
             dy = DySpec(p1=self.dec.dskip(l - 1), pool_dy=self.dpooled[l], pool_idx=self.idx[l])
         self.init.bwd(self.xin_v, dy, None, accumulate)
+
+
+    # --------------------------------------------------------- explainability
+    def tap_names(self) -> List[str]:
+        nl = self.L - 1
+        return (["init_conv"] + [f"encoders.{i}.conv" for i in range(nl)]
+                + [f"decoders.{j}{sfx}" for j in range(nl) for sfx in ("", ".conv")])
+
+    def resolve_tap(self, name: str) -> Tuple[str, int]:
+        """("enc" | "dec", level) of a reference module name (gradcam.py hooks: the modules whose output is a
+        tensor; `encoders.{i}` returns a tuple there and is no valid name here either)."""
+        n = name[len("backbone."):] if name.startswith("backbone.") else name
+        nl = self.L - 1
+        if n == "init_conv":
+            return "enc", 0
+        m = re.fullmatch(r"encoders\.(\d+)\.conv", n)
+        if m and int(m.group(1)) < nl:
+            return "enc", int(m.group(1)) + 1
+        m = re.fullmatch(r"decoders\.(\d+)(\.conv)?", n)
+        if m and int(m.group(1)) < nl:
+            return "dec", nl - 1 - int(m.group(1))
+        raise _unknown_tap(name, self.tap_names())
+
+    def explain(self, x: torch.Tensor, dlogits: Seed, taps: Sequence[str] = (), input_grad: bool = False,
+                dx: Optional[torch.Tensor] = None, accumulate: bool = False) -> ExplainResult:
+        """Eval forward, then the data-only backward of the seed gradient `dlogits` (a tensor, or a function of the
+        logits): no weight / bias gradient is launched and nothing is written to the gradient arena.  Returns the
+        tapped layers' activations and gradient sources, and with input_grad the input gradient dx (summed into a
+        given dx when accumulate)."""
+        where = [self.resolve_tap(t) for t in taps]
+        dx = _explain_input(x, dx, input_grad)
+        logits = self.forward(x, training=False)
+        acts = [_snapshot(self.level_out(l) if kind == "enc" else self.dec.dout[l]) for kind, l in where]
+        seed = _seed(dlogits, logits)
+        rt = self.rt
+        rt.data_only = True
+        try:
+            dbottom = self.dec.bwd(self.bottom, seed, False)
+            if input_grad or any(kind == "enc" for kind, _ in where):
+                dy = DySpec(p1=dbottom)
+                for l in range(self.L - 1, 0, -1):
+                    self.enc[l - 1].bwd(self.pooled[l], dy, self.dpooled[l], False)
+                    dy = DySpec(p1=self.dec.dskip(l - 1), pool_dy=self.dpooled[l], pool_idx=self.idx[l])
+                if input_grad:
+                    self.init.bwd(self.xin_v, dy, None, False)
+                    _stem_dgrad(rt, self.init, dx, 0, accumulate)
+        finally:
+            rt.data_only = False
+            rt.join_side()
+        out = {}
+        for name, (kind, l), act in zip(taps, where, acts):
+            if kind == "dec":
+                grad = DySpec(p1=self.dec.dout[l])      # (the consumer's backward wrote d(out) over out)
+            elif l == self.L - 1:
+                grad = DySpec(p1=self.bottom)
+            else:
+                grad = DySpec(p1=self.dec.dskip(l), pool_dy=self.dpooled[l + 1], pool_idx=self.idx[l + 1])
+            out[name] = Tap(name, act, self.dims[l], self.F[l], grad)
+        return ExplainResult(logits, out, dx)
 
 
 class DualEncoderProgram:
@@ -677,6 +798,70 @@ class DualEncoderProgram:
                 streams[0].wait_stream(streams[m])
         for m in range(M):                           # big levels: one stream
             levels(m, split, 0)
+
+
+    # --------------------------------------------------------- explainability
+    def tap_names(self) -> List[str]:
+        nl = self.L - 1
+        names = []
+        for m in range(self.M):
+            names += [f"encoders.{m}.init_conv"] + [f"encoders.{m}.blocks.{i}.conv" for i in range(nl)]
+        return names + [f"decoder.{j}{sfx}" for j in range(nl) for sfx in ("", ".conv")]
+
+    def resolve_tap(self, name: str) -> Tuple[str, int, int]:
+        """("enc", modality, level) | ("dec", 0, level) of a reference module name."""
+        n = name[len("backbone."):] if name.startswith("backbone.") else name
+        nl = self.L - 1
+        m = re.fullmatch(r"encoders\.(\d+)\.init_conv", n)
+        if m and int(m.group(1)) < self.M:
+            return "enc", int(m.group(1)), 0
+        m = re.fullmatch(r"encoders\.(\d+)\.blocks\.(\d+)\.conv", n)
+        if m and int(m.group(1)) < self.M and int(m.group(2)) < nl:
+            return "enc", int(m.group(1)), int(m.group(2)) + 1
+        m = re.fullmatch(r"decoder\.(\d+)(\.conv)?", n)
+        if m and int(m.group(1)) < nl:
+            return "dec", 0, nl - 1 - int(m.group(1))
+        raise _unknown_tap(name, self.tap_names())
+
+    def explain(self, x: torch.Tensor, dlogits: Seed, taps: Sequence[str] = (), input_grad: bool = False,
+                dx: Optional[torch.Tensor] = None, accumulate: bool = False) -> ExplainResult:
+        """UNetProgram.explain for the DualEncoder.  Encoder taps and the input gradient run the encoders' backward,
+        which is data-only for mean / add fusion; concat and attention fusion serve the decoder taps only."""
+        where = [self.resolve_tap(t) for t in taps]
+        enc_taps = [t for t, w in zip(taps, where) if w[0] == "enc"]
+        if self.fusion not in ("mean", "add") and (enc_taps or input_grad):
+            what = f"layer {enc_taps[0]!r}" if enc_taps else "the input gradient"
+            raise NotImplementedError(f"explain: {what} under {self.fusion} fusion (the encoders' data-only backward "
+                                      "covers mean / add fusion; decoder.{j} layers work for every fusion)")
+        dx = _explain_input(x, dx, input_grad)
+        logits = self.forward(x, training=False)
+        if enc_taps:
+            self.materialize_features()
+        acts = [_snapshot(self.y[m][l] if kind == "enc" else self.dec.dout[l]) for kind, m, l in where]
+        seed = _seed(dlogits, logits)
+        rt = self.rt
+        rt.data_only = True
+        try:
+            self.dec.bwd(self.bottom, seed, False)
+            if enc_taps or input_grad:
+                self._encoders_bwd_streams(False)
+                if input_grad:
+                    for m in range(self.M):
+                        _stem_dgrad(rt, self.encs[m][0], dx, m, accumulate)
+        finally:
+            rt.data_only = False
+            rt.join_side()
+        sc = 1.0 if self.fusion == "add" else 1.0 / self.M
+        out = {}
+        for name, (kind, m, l), act in zip(taps, where, acts):
+            if kind == "dec":
+                grad = DySpec(p1=self.dec.dout[l])
+            else:                                       # the DySpec the encoders' backward gathers for this block
+                grad = DySpec(p1=self.dfused(l), scale1=sc)
+                if l < self.L - 1:
+                    grad.pool_dy, grad.pool_idx = self.dpooled[m][l + 1], self.idx[m][l + 1]
+            out[name] = Tap(name, act, self.dims[l], self.F[l], grad)
+        return ExplainResult(logits, out, dx)
 
 
 def _ptr_array(ptrs):

@@ -112,6 +112,9 @@ class Runtime:
         self._wred_active = False
         self._wred_session = 0          # id of the current backward session (own_part's reuse check)
         self._wred_flush_hook = None    # DP: flushes the queued reduces before a gradient bucket is reduced
+        # explainability (SegEngine.explain): the backward launches data gradients only -- no weight / bias gradient,
+        # no split reduce, nothing written to the gradient arena
+        self.data_only = False
 
     # ---------------------------------------------------------------- alloc
     def act(self, N: int, D: int, H: int, W: int, C: int, ld: Optional[int] = None) -> Act:
