@@ -11,6 +11,7 @@
 // of the library's ABI).  Keep them few: one launcher per kernel family.
 #pragma once
 #include "mmseg_common.h"
+#include "instnorm_ops.h"   // norm_relu8: the deferred norm of staged channels
 
 #include <stdlib.h>
 
@@ -150,16 +151,6 @@ template <typename T>
 __device__ __forceinline__ T* out_at(const GemmArgs& g, long long vox, int col) {
   if (g.out2 && col >= g.split) return reinterpret_cast<T*>(g.out2) + vox * g.ldo2 + (col - g.split);
   return reinterpret_cast<T*>(g.out) + vox * g.ldo + col;
-}
-
-// The deferred norm of 8 staged channels: relu((v - mu) * rs) rounded to T, in_relu_apply's operations.
-template <typename T>
-__device__ __forceinline__ void norm_relu8(V8<T>& v, const float* mu, const float* rs) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float h = (v.get(j) - mu[j]) * rs[j];
-    v.set(j, h > 0.f ? h : 0.f);
-  }
 }
 
 // 32-channel K chunks a CONV3 brick kernel iterates: all of the (power-of-two) A source's, or only the

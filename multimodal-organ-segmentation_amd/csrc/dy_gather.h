@@ -1,5 +1,5 @@
 // The gathered gradient of an InstanceNorm + ReLU output (DySrc / DyCtx), shared by the norm backward kernels
-// (norm_pool.hip) and the Grad-CAM channel weights (explain.hip): one gather, one set of bits.
+// (instnorm.hip) and the Grad-CAM channel weights (explain.hip): one gather, one set of bits.
 #pragma once
 #include "mmseg_common.h"
 

@@ -91,7 +91,7 @@ __global__ void seed_fill(const float* __restrict__ x, int C, long long V, int c
 }
 
 // --------------------------------------------------------------- weights
-// Block = (256 / C8) voxel lanes x C8 channel groups, a thread owns 8 channels (norm_pool.hip's layout); chunk b of
+// Block = (256 / C8) voxel lanes x C8 channel groups, a thread owns 8 channels (instnorm.hip's layout); chunk b of
 // the voxels -> part[b][C].  MODE 0: sum_v g.  MODE 1: sum_v alpha g over g > 0, alpha = g^2 / (2 g^2 + S g^3 + 1e-8)
 // with S = sum_v A per channel (suma).  MODE 2: sum_v A (Grad-CAM++'s first pass; no gradient read).
 template <typename T, int MODE>

@@ -1228,7 +1228,7 @@ __global__ __launch_bounds__(256, (NC <= 6 && sizeof(T) == 2) ? 2 : 1) void head
   }
   __syncthreads();
   const long long blk = (long long)n * nchunk + chunk;
-  if (do_in && threadIdx.x < Cin) {   // in the layout of norm_pool.hip in_bwd_partial: [n][chunk][c][2]
+  if (do_in && threadIdx.x < Cin) {   // in the layout of instnorm.hip in_bwd_partial: [n][chunk][c][2]
     const int c = threadIdx.x;
     float* ip = inpart + (blk * Cin + c) * 2;
     ip[0] = ired[0][0][c] + ired[1][0][c] + ired[2][0][c] + ired[3][0][c];

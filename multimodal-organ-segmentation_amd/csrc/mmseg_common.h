@@ -111,6 +111,14 @@ __device__ __forceinline__ double wave_sum_d(double x) {
 
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Host: the storage type of an entry point's `dtype` argument as a tag value, fn(bf16_t{}) or fn(float{}); a launcher
+// written as a generic lambda reads it with `using T = decltype(tag)`.
+template <typename F>
+static inline void by_dtype(int dtype, F&& fn) {
+  if (dtype == MMSEG_BF16) fn(bf16_t{});
+  else fn(float{});
+}
+
 // 3x3x3 tap t in [0,27): (kz, ky, kx) = (t/9, (t/3)%3, t%3), offsets -1..1.
 __device__ __forceinline__ void tap_delta(int t, int& dz, int& dy, int& dx) {
   dz = t / 9 - 1;

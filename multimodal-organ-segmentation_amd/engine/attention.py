@@ -1,6 +1,6 @@
 """Multi-head cross-attention of CrossAttentionFusion (reference
 src/models/fusion/attention_fusion.py:77-164) as a fixed sequence of HIP
-launches (csrc/attention.hip + the InstanceNorm kernels of norm_pool.hip).
+launches (csrc/attention.hip + the InstanceNorm kernels of instnorm.hip).
 
 Layout: features are NDHWC [B][V][C] in the engine storage dtype; head h is
 the channel slice [h*hd, (h+1)*hd) (the reference's view(B, heads, hd, V),

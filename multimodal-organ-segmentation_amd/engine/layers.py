@@ -202,7 +202,7 @@ def _wgrad_ksplit(rows: int, ncols: int, V: int) -> int:
     return max(1, min(-(-TARGET_BLOCKS // tiles), V // 512))
 
 
-SMALL_IN_V = 4096   # norm_pool.hip knob_small_v(): at or below it InstanceNorm is one launch (stats + apply)
+SMALL_IN_V = 4096   # instnorm.hip knob_small_v(): at or below it InstanceNorm is one launch (stats + apply)
 
 
 @dataclass

@@ -23,12 +23,9 @@ import torch
 import torch.nn as nn
 
 from .._lib import ptr
-from .layers import Block, ConvT2, DySpec, GroupBlock, Head, Packer, Point, act_group_view
+from .layers import SMALL_IN_V, Block, ConvT2, DySpec, GroupBlock, Head, Packer, Point, act_group_view
 from .profiler import TIMER
 from .runtime import Act, FlatParams, Runtime
-
-
-SMALL_IN_V = 4096   # norm_pool.hip knob_small_v(): at or below it InstanceNorm is one launch (stats + apply)
 
 
 @dataclass

@@ -19,7 +19,7 @@ bias, shifted-window mask; engine/attention.py on mmseg_bgemm_nt MFMA),
 token linears as 1x1 implicit GEMMs (mmseg_conv_gemm MODE_POINT) with
 split-K weight gradients (mmseg_wgrad + mmseg_wgrad_reduce), UNETR convs on
 the same conv kernels as UNet3D, InstanceNorm statistics / backward from
-norm_pool.hip, the LeakyReLU residual tail (mmseg_res_apply / _lrelu_bwd).
+instnorm.hip, the LeakyReLU residual tail (mmseg_res_apply / _lrelu_bwd).
 """
 from __future__ import annotations
 
@@ -33,8 +33,8 @@ import torch.nn as nn
 
 from .._lib import ptr
 from .attention import WindowAttentionEngine
-from .layers import (MODE_POINT, Conv3, ConvT2, Head, Packer, _col_tile, _gemm_ksplit, _gemm_name, _io_bytes,
-                     _own_part, _wgrad_ksplit)
+from .layers import (MODE_POINT, SMALL_IN_V, Conv3, ConvT2, Head, Packer, _col_tile, _gemm_ksplit, _gemm_name,
+                     _io_bytes, _own_part, _wgrad_ksplit)
 from .profiler import TIMER
 from .runtime import Act, FlatParams, Runtime, round_up
 
@@ -547,7 +547,7 @@ class ResBlockProg:
         # the tail's LeakyReLU backward and the norms' partial sums in one pass (mmseg_lrelu_bwd_in_part) above the
         # one-launch small-volume norms; MMSEG_RES_FUSE=0 keeps the separate passes (bitwise the same)
         V = D * H * W
-        nch = rt.lib.mmseg_instnorm_part_chunks(V, self.cout) if V > 4096 else 0
+        nch = rt.lib.mmseg_instnorm_part_chunks(V, self.cout) if V > SMALL_IN_V else 0
         self.res_nch = nch if _res_fuse() else 0
         if self.res_nch:
             p = lambda: torch.empty(N * nch * self.cout * 2, dtype=torch.float32, device=rt.device)

@@ -1,6 +1,7 @@
-"""The DualEncoder fusion path's kernels (csrc/norm_pool.hip) against the fp64 restatement tests/fusion_ref.py:
-modality fusion forward (as stored and over pre-norm sources), max-pool over pre-norm sources, the attention gate
-and its backward, and the InstanceNorm backward with every source of its gathered dy.
+"""The DualEncoder fusion path's kernels (csrc/instnorm.hip, csrc/pool_fuse.hip) against the fp64 restatement
+tests/fusion_ref.py: modality fusion forward (as stored and over pre-norm sources), max-pool over pre-norm sources,
+the attention gate and its backward, the InstanceNorm forward through every kernel, and the InstanceNorm backward
+with every source of its gathered dy.
 
 Every input -- statistics, gate weights, argmax codes -- is built here from the reference side; only
 test_attention_fusion_composite feeds kernels with kernel outputs.  Input rows are wider than C with the padding
@@ -482,6 +483,53 @@ def _strided(vals, stride, off, dev, span):
         buf[n * stride + off:n * stride + off + k] = vals[n]
     buf = buf.to(dev)
     return buf, buf.data_ptr() + off * 4
+
+
+# Worst error (tests.helpers.rel) of the kernels' fp32 mean / rstd against the fp64 statistics over the 96 cases of
+# test_instnorm_fwd_every_kernel, measured on an MI355X with the library as it was before the InstanceNorm reductions
+# got one definition each.  The bounds are 4x that: the fp32 rounding of a Welford pass depends on the input and
+# moves either figure by a few ulp.
+MEAN_MEASURED, RSTD_MEASURED = 2.276e-7, 2.281e-7
+MEAN_TOL, RSTD_TOL = 4 * MEAN_MEASURED, 4 * RSTD_MEASURED
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("C", [8, 24, 64])
+@pytest.mark.parametrize("small_v", ["16384", "0"])
+@pytest.mark.parametrize("shape", IN_SHAPES)
+def test_instnorm_fwd_every_kernel(dev, dtype, shape, small_v, C, relu, monkeypatch):
+    """mmseg_instnorm_fwd through every forward kernel: in_small_fwd_r<1>, both sizes of in_small_fwd_r<8> and
+    in_small_fwd (small_v 16384), or in_stats_partial / _finalize / in_relu_apply (small_v 0; C = 24 takes the
+    partial kernels' serial reduction, 8 and 64 the shuffle tree), with and without the ReLU, on strided rows.
+    y against the fp64 reference, mean / rstd against the fp64 statistics, nothing written past C -- and y equal bit
+    for bit to what mmseg_instnorm_apply writes from the returned mean / rstd: every forward kernel normalises with
+    in_relu_apply's expression."""
+    monkeypatch.setenv("MMSEG_IN_SMALL_V", small_v)
+    N, (D, H, W) = 2, shape
+    V, ldx, ldy = D * H * W, C + 8, C + 16
+    L, s = lib(), stream_handle()
+    x = _norm_input(dtype, N, C, shape)[0]
+    mean, rstd = R.in_stats(x)
+    xr = _rows(x, dtype, ldx, dev)
+    y = torch.full((N * V, ldy), SENT, dtype=dtype, device=dev)
+    stats = torch.full((2, N * C + 8), SENT, device=dev)
+    ws = torch.empty(L.mmseg_instnorm_ws_floats(N, V, C), device=dev)
+    L.mmseg_instnorm_fwd(ptr(xr), ldx, ptr(y), ldy, N, V, C, 1e-5, ptr(stats[0]), C, ptr(stats[1]), relu, ptr(ws),
+                         _code(dtype), s)
+    torch.cuda.synchronize()
+    ref = (x - _bc(mean)) * _bc(rstd)
+    ey = rel(_unrows(y, N, C, D, H, W), torch.relu(ref) if relu else ref)
+    em, er = rel(stats[0, :N * C].view(N, C), mean), rel(stats[1, :N * C].view(N, C), rstd)
+    print(f"instnorm_fwd: y {ey:.3e}, mean {em:.3e}, rstd {er:.3e}")
+    assert ey < TOL[dtype]
+    assert (y[:, C:] == SENT).all() and (stats[:, N * C:] == SENT).all()
+    assert em < MEAN_TOL and er < RSTD_TOL
+    y2 = torch.full_like(y, SENT)
+    L.mmseg_instnorm_apply(ptr(xr), ldx, ptr(y2), ldy, N, V, C, ptr(stats[0]), ptr(stats[1]), relu, _code(dtype), s)
+    torch.cuda.synchronize()
+    bits = torch.int32 if dtype == torch.float32 else torch.int16
+    assert torch.equal(y.view(bits), y2.view(bits))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
