@@ -59,7 +59,7 @@ def test_head_loss_size_queries_agree():
     weight-gradient partials it writes and the InstanceNorm partials it hands to mmseg_instnorm_bwd_part must be
     counted over the same chunks, and the loss workspace over the statistics pass's."""
     L = _lib.lib()
-    for N, V in ((2, 96 ** 3), (1, 64 ** 3), (2, 32 ** 3), (1, 7)):
+    for N, V in ((2, 96 ** 3), (1, 64 ** 3), (2, 32 ** 3), (1, 7), (2, 3535), (2, 45)):
         for C in (3, 6, 7):
             nch = L.mmseg_head_loss_in_chunks(C, 32, V)
             assert nch >= 1
@@ -67,3 +67,11 @@ def test_head_loss_size_queries_agree():
             assert L.mmseg_loss_ws_floats(N, C, V) >= N * (3 * C + 3) + 2 * N * C + 2
     assert L.mmseg_head_loss_in_chunks(6, 32, 96 ** 3) == 256   # 3,456 voxels per block at 96^3
     assert L.mmseg_head_loss_in_chunks(6, 16, 96 ** 3) == 0     # partials only for Cin = 32
+    # the ragged volumes of tests/test_loss_head_gpu.py: 3535 voxels are 3 statistics chunks (of 1179) and 2 backward
+    # chunks (of 1768), 45 voxels one of each
+    for V, stat_chunks, bwd_chunks in ((3535, 3, 2), (45, 1, 1)):
+        for C in (2, 5, 8):
+            assert L.mmseg_loss_ws_floats(2, C, V) == 2 * stat_chunks * (3 * C + 3) + 2 * 2 * C + 2
+            assert L.mmseg_head_loss_in_chunks(C, 32, V) == bwd_chunks
+            for Cin in (8, 16, 32):
+                assert L.mmseg_head_loss_wpart_floats(C, Cin, 2, V) == 2 * bwd_chunks * (C * Cin + C)
