@@ -12,6 +12,7 @@ import mmseg_amd  # noqa: F401
 from mmseg_amd.engine.layers import Conv3, ConvT2, DySpec, Head, Point, Block
 from mmseg_amd.engine.runtime import Act, FlatParams, Runtime
 from mmseg_amd._lib import lib, ptr, stream_handle
+from tests.conv_fused_cases import VARIANTS, variant_names
 from tests.helpers import from_ndhwc, golden, rel, to_ndhwc
 
 pytestmark = pytest.mark.gpu
@@ -50,54 +51,15 @@ def test_conv3_fwd_dgrad_wgrad(dev, dtype, cin, cout, shape):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("knobs,cin,cout,shape", [
-    # brick v2 variants (kernel choice is by grid size; the knobs force each one on a small grid)
-    ({"MMSEG_BRICK2_MINBLK": "0"}, 64, 64, (2, 8, 16, 8)),          # BN64 ZW1
-    ({"MMSEG_BRICK2_MINBLK": "0"}, 32, 128, (1, 4, 8, 16)),         # BN64 ZW1, 2 column tiles
-    # brick v3 (bf16 BN32 default; f32 takes v2): persistent blocks over several bricks / column tiles
-    ({"MMSEG_BRICK3_BLOCKS": "3"}, 64, 128, (1, 4, 16, 16)),         # 4 col tiles x 4 bricks, ragged ranges
-    ({"MMSEG_BRICK3_BLOCKS": "0"}, 64, 32, (1, 12, 8, 24)),          # one unit per block, border (2 chunks)
-    # brick v4 (bf16, Cin 32, register-resident weights, double-buffered halo; f32 takes v2)
-    ({"MMSEG_BRICK4_BLOCKS": "3"}, 32, 32, (2, 8, 16, 8)),           # 8 bricks over 3 blocks, ragged ranges
-    ({"MMSEG_BRICK4_BLOCKS": "4"}, 32, 64, (1, 4, 8, 16)),           # 2 column tiles x 2 blocks each
-    ({}, 32, 32, (1, 12, 8, 24)),                                    # one brick per block, border bricks
-    # brick v6 (W % 16: 4x4x16 bricks, ky-shared A fragments, the staging interleaved between the MFMAs)
-    ({"MMSEG_BRICK4_BLOCKS": "1"}, 32, 32, (2, 8, 16, 16)),          # one block over all 16 bricks of 2 samples
-    ({"MMSEG_BRICK4_BLOCKS": "3"}, 32, 32, (2, 8, 8, 32)),           # 16 bricks over 3 blocks, ragged ranges
-    ({}, 32, 32, (1, 12, 12, 16)),                                   # border bricks on every side
-    ({"MMSEG_BRICK4_BLOCKS": "4"}, 32, 64, (1, 4, 4, 32)),           # 2 column tiles
-    ({"MMSEG_BRICK4_BLOCKS": "1"}, 32, 32, (2, 4, 4, 16)),           # one brick per sample
-    ({}, 128, 32, (1, 4, 16, 8)),                                   # BN32 ZW1, 4 input chunks
-    ({}, 256, 128, (2, 12, 12, 12)),                                 # runtime brick (3,6,12) + chunk split-K
-    ({}, 512, 256, (1, 6, 6, 6)),                                    # runtime brick (6,6,6), 16 chunks
-    # runtime brick 6x6x6 with the in-block K split over two 256-thread halves (KW = 2, bf16; r05), and an odd chunk
-    # count per block (2 + 1: half 1 idles through the last stages' barriers)
-    ({}, 256, 256, (4, 12, 12, 12)),                                 # the grouped 12^3 shape (N = M x B = 4)
-    ({"MMSEG_BRICKR_SLOTS": "6"}, 256, 32, (2, 6, 6, 6)),           # 8 chunks over 3 splits: 3 (2 + 1), 3, 2
-    ({"MMSEG_BRICKR_SLOTS": "1"}, 128, 32, (2, 6, 6, 6)),
-    ({"MMSEG_WGRAD_BRICK": "1"}, 64, 128, (2, 4, 8, 8)),             # v1 brick wgrad (32 co per block)
-    ({"MMSEG_WGRAD_BRICK": "0"}, 64, 64, (1, 4, 8, 8)),              # generic wgrad
-    ({}, 32, 128, (1, 8, 4, 16)),                                    # v2 brick wgrad, 2 row tiles of 64 co
-    ({}, 64, 32, (2, 4, 4, 16)),                                     # v2 brick wgrad, 32 co per block
-    # v2 brick wgrad with LDS-DMA staging (bf16; f32 keeps the register-staged kernel): 3-stage ring, border
-    # halos, ragged brick ranges over the splits
-    ({"MMSEG_WGRAD_DMA": "1"}, 32, 128, (1, 8, 4, 16)),              # 64 co, 2 row tiles
-    ({"MMSEG_WGRAD_DMA": "1"}, 64, 32, (2, 4, 4, 16)),               # 32 co, 2 input chunks
-    ({"MMSEG_WGRAD_DMA": "1"}, 32, 32, (2, 12, 8, 24)),              # 32 co, 36 bricks
-    ({"MMSEG_WGRAD_DMA": "1"}, 64, 64, (1, 8, 12, 16)),              # 64 co, 24 bricks
-    ({"MMSEG_BRICK": "1"}, 64, 64, (2, 8, 8, 8)),                   # v1 brick
-    ({"MMSEG_BRICK": "0"}, 64, 64, (2, 8, 8, 8)),                   # per-lane gather GEMM
-    # brick v8 (bf16; f32 ignores the knob): 8 waves over an 8x8x8 brick, LDS-DMA halo + double-buffered weights
-    ({"MMSEG_BRICK8": "2", "MMSEG_BRICK8_MINBLK": "0"}, 64, 64, (2, 8, 16, 8)),     # 2 chunks (halo refill)
-    ({"MMSEG_BRICK8": "2", "MMSEG_BRICK8_MINBLK": "0"}, 32, 64, (1, 16, 8, 24)),    # 1 chunk, border bricks
-    ({"MMSEG_BRICK8": "2", "MMSEG_BRICK8_MINBLK": "0"}, 128, 128, (1, 8, 8, 16)),   # 4 chunks, 2 column tiles
-    ({"MMSEG_BRICK8": "2", "MMSEG_BRICK8_MINBLK": "0"}, 64, 32, (1, 16, 8, 16)),    # BN32: 2 planes per wave
-    ({"MMSEG_BRICK8": "2", "MMSEG_BRICK8_MINBLK": "0"}, 128, 32, (2, 16, 16, 8)),   # BN32, 4 chunks, border
-])
+@pytest.mark.parametrize("knobs,cin,cout,shape", [row[:4] for row in VARIANTS])
 def test_conv3_kernel_variants(dev, dtype, knobs, cin, cout, shape, monkeypatch):
+    """Every kernel variant of the 3^3 conv against fp64, on the rows of tests/conv_fused_cases.py VARIANTS (each
+    names the kernel it is for); the forward, data-gradient and weight-gradient kernels that ran are the row's
+    (tests/test_conv_fused_plan_cpu.py holds the same names against the planning queries without a GPU)."""
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
-    _check_conv3(dev, dtype, cin, cout, shape)
+    ran = _check_conv3(dev, dtype, cin, cout, shape)
+    assert ran == variant_names(knobs, cin, cout, shape)[0 if dtype == torch.float32 else 1]
 
 
 def _planned_fwd(layer, x, y):
@@ -155,6 +117,8 @@ def test_b32_halo_staging(dev, dtype, cin, cout, shape, extra, kernel, monkeypat
 
 
 def _check_conv3(dev, dtype, cin, cout, shape):
+    """Forward, data gradient, weight and bias gradient of one Conv3 against fp64; returns the kernels that ran
+    (forward, data gradient) and the weight-gradient kernel the library names for Conv3._bwd's arguments."""
     torch.manual_seed(cin + cout)
     conv = nn.Conv3d(cin, cout, 3, padding=1).to(dev)
     rt = Runtime(dev, dtype)
@@ -166,6 +130,7 @@ def _check_conv3(dev, dtype, cin, cout, shape):
     ya = rt.act(N, D, H, W, cout)
     layer.pack()
     layer.fwd(xa, ya)
+    ran_fwd = lib().mmseg_last_kernel().decode()
     xd = _q(x, dtype).requires_grad_(True)
     wd = _q(conv.weight, dtype).requires_grad_(True)
     bd = conv.bias.detach().double().cpu().requires_grad_(True)
@@ -176,10 +141,16 @@ def _check_conv3(dev, dtype, cin, cout, shape):
     dya = _act(dy, dtype)
     dxa = rt.act(N, D, H, W, cin)
     layer.bwd(xa, dya, dxa, accumulate=False)
+    ran_dgrad = lib().mmseg_last_kernel().decode()     # the data gradient is the backward's last launch
     (ref * _q(dy, dtype)).sum().backward()
     assert rel(from_ndhwc(dxa.buf, N, cin, D, H, W), xd.grad) < TOL[dtype]
     assert rel(flat.grad(conv.weight), wd.grad) < GTOL[dtype]
     assert rel(flat.grad(conv.bias), bd.grad) < GTOL[dtype]
+    # the weight-gradient kernel: the name query with the arguments Conv3._bwd passes
+    L, V = lib(), N * D * H * W
+    wshape = (V, layer.Co, layer.Cip, layer.Ci, layer.cpg_shift, D, H, W, dya.ld, xa.ld)
+    wsf = L.mmseg_conv3_wgrad_ws_floats(*wshape, rt.code)
+    return ran_fwd, ran_dgrad, L.mmseg_conv3_wgrad_kernel(*wshape, wsf, 0, rt.code).decode()
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
