@@ -508,6 +508,40 @@ int mmseg_augment(const float* src, int C, int D, int H, int W, const void* labe
                   int rot_k, const float* scale, const float* shift, int noise, double noise_mean, float noise_sd,
                   const unsigned long long* noise_key, float* dst, void* label_dst, void* stream);
 
+/* ------------------------------------------------------- training patches */
+/* Foreground-biased crops with rotation and scaling out of a volume that is resident on the device
+ * (csrc/patch.hip, data/patch.py; the reference's RandomCrop / CenterCrop, transforms.py:142-212, are the
+ * plain-copy case).  label [D][H][W] int64 / uint8 by label_bytes, C <= 4, P <= 16 patches per launch.
+ * Array arguments are host arrays unless they are called device arrays; nothing is read back.
+ *
+ * mmseg_fg_count: counts[mmseg_fg_chunks(D*H*W)] (device int32) = voxels with label > 0 in each chunk of
+ * consecutive voxels of the row-major volume.  The counts depend on the label alone.
+ *
+ * mmseg_patch_pick: crop starts of P patches of (pd, ph, pw) voxels into starts [P][3] (device int32).
+ * mode[p] 0: fallback_start[p] (which must lie inside 0 .. n_a - P_a on every axis with n_a >= P_a).
+ * mode[p] 1: with n the total of the counts, fallback_start[p] if n == 0, else the k-th voxel v (row-major)
+ * with label > 0, k = min((long long)floor(u[p] * n), n - 1) in one fp64 multiply, and
+ * start_a = clamp(v_a - P_a / 2, 0, n_a - P_a).  In both modes an axis with n_a < P_a gets
+ * start_a = -((P_a - n_a) / 2): the volume is centred in the patch.  label and counts may be NULL when
+ * every mode is 0.
+ *
+ * mmseg_patch_sample: src [C][D][H][W] fp32 and label (NULL = none) -> dst [P][C][pd][ph][pw] and label_dst
+ * [P][pd][ph][pw], starts a device array as mmseg_patch_pick writes it.  affine[p] == 0: dst[o] =
+ * src[start + o], pad_value[c] (labels: 0) outside the volume.  affine[p] != 0: with q = o - (P - 1) / 2,
+ * c = start + (P - 1) / 2 and M = M[p*9 .. +9) row-major, p_a = ((M[a][0] q_0 + M[a][1] q_1) + M[a][2] q_2)
+ * + c_a in fp64, every product and sum rounded on its own; the image is trilinear over the 8 corners of
+ * floor(p), a corner outside the volume contributing pad_value[c] (scipy.ndimage.affine_transform order 1,
+ * mode "grid-constant"), accumulated z, then y, then x as a w0 + b w1 in fp64 and rounded once to fp32; the
+ * label is the voxel at floor(p_a + 0.5), 0 outside. */
+int mmseg_fg_chunks(long long V);
+int mmseg_fg_count(const void* label, int label_bytes, int D, int H, int W, int* counts, void* stream);
+int mmseg_patch_pick(const void* label, int label_bytes, int D, int H, int W, const int* counts, int P, int pd,
+                     int ph, int pw, const int* mode, const double* u, const int* fallback_start, int* starts,
+                     void* stream);
+int mmseg_patch_sample(const float* src, int C, int D, int H, int W, const void* label, int label_bytes,
+                       const int* starts, int P, int pd, int ph, int pw, const int* affine, const double* M,
+                       const float* pad_value, float* dst, void* label_dst, void* stream);
+
 /* ------------------------------------------------------------ NIfTI volumes */
 /* The voxel block of a NIfTI-1 file decoded on the device (replaces load_nifti's get_fdata().astype and the
  * np.stack(...).copy() of dataset.py:95-113): raw = X*Y*Z elements exactly as the file holds them (x fastest;

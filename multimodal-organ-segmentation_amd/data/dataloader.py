@@ -6,7 +6,9 @@ resizes them on the GPU (data/nifti.py).  With data.synthetic it serves the seed
 phantoms of data/synthetic.py in the same batch format.  Under data parallelism each rank takes samples r, r+W, ...
 (DistributedSampler semantics).  With data.synthetic.device: true
 the phantoms are generated and normalised on the GPU instead (data/device.py), and
-data.augmentation.enabled: true augments the training split there (data/augment.py)."""
+data.augmentation.enabled: true augments the training split there (data/augment.py).  data.patch.enabled: true
+trains on patches drawn from the volumes at their own size and validates on the full-size volumes
+(data/patch.py); with the key absent or false nothing changes."""
 from typing import Any, Dict
 
 import torch
@@ -32,7 +34,40 @@ def get_dataset(config: Dict[str, Any], split: str = "train"):
                                seed=seed)
 
 
+def _patch_dataloader(config: Dict[str, Any], patch_cfg: Dict[str, Any], split: str, shuffle):
+    """data.patch.enabled: the training split draws patches from volumes at their own size (data/patch.py); val /
+    test yield the full-size volumes one by one, for the sliding windows of Trainer._validate."""
+    from .augment import DeviceAugment
+    from .device import DeviceLoader, DevicePhantomDataset
+    from .patch import DevicePatchDataset, PatchLoader
+    syn = config["data"].get("synthetic")
+    if syn is None:
+        from .nifti import DeviceNiftiDataset, read_data_list
+        ds = DeviceNiftiDataset(config, read_data_list(config, split), mode=split, resize=False)
+    elif syn.get("device", False):
+        n = syn["n_train"] if split == "train" else syn.get("n_val", 2)
+        seed = syn.get("seed", 1234) + (0 if split == "train" else 100000)
+        ds = DevicePhantomDataset(n, syn.get("size", 96), config["model"]["out_channels"],
+                                  config["data"]["modalities"], torch.device("cuda", torch.cuda.current_device()),
+                                  seed=seed, preprocessing=config["data"].get("preprocessing"))
+    else:
+        raise NotImplementedError("data.patch.enabled needs the device data path: NIfTI lists or "
+                                  "data.synthetic.device: true (the sampler is a HIP pass, there is no CPU path)")
+    if split != "train":
+        return DeviceLoader(ds, 1, shuffle=False if shuffle is None else shuffle, drop_last=False, seed=ds.seed,
+                            pad=False)
+    aug_cfg = config["data"].get("augmentation") or {}
+    augment = DeviceAugment(aug_cfg) if aug_cfg.get("enabled", False) else None
+    return PatchLoader(DevicePatchDataset(ds, patch_cfg, augment=augment), config["training"]["batch_size"],
+                       shuffle=True if shuffle is None else shuffle, seed=ds.seed)
+
+
 def get_dataloader(config: Dict[str, Any], split: str = "train", shuffle=None, drop_last=None):
+    patch_cfg = config["data"].get("patch")
+    if patch_cfg is not None:
+        from .patch import patch_config
+        if patch_config(patch_cfg)["enabled"]:
+            return _patch_dataloader(config, patch_cfg, split, shuffle)
     if config["data"].get("synthetic") is None:
         from .device import DeviceLoader
         ds = get_dataset(config, split)

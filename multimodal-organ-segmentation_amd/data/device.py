@@ -159,11 +159,16 @@ class DevicePhantomDataset:
     def __getitem__(self, i: int) -> Dict[str, Any]:
         return self.get(i, 0)
 
+    def volume(self, i: int):
+        """Phantom i generated and normalised: (image [M, S, S, S] fp32, label [S, S, S], patient_id)."""
+        image, label = device_phantom(self.seed + i, self.size, self.C, self.mods, self.device)
+        self.norm(image)
+        return image, label, f"synthetic_{self.seed + i}"
+
     def get(self, i: int, epoch: int) -> Dict[str, Any]:
         """Sample i as epoch `epoch` sees it: normalise, augment, resize (the reference's order,
         transforms.py:418-451).  Without augmentation the epoch changes nothing."""
-        image, label = device_phantom(self.seed + i, self.size, self.C, self.mods, self.device)
-        self.norm(image)
+        image, label, _ = self.volume(i)
         sample = {"image": image, "label": label}
         if self.augment is not None:
             sample = self.augment(sample, epoch, i, self.seed)

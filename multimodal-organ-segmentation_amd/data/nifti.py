@@ -135,7 +135,7 @@ class DeviceNiftiDataset:
     in the reference's batch format.  Serves DeviceLoader like DevicePhantomDataset (get, __len__, mods)."""
 
     def __init__(self, config: Dict[str, Any], rows: List[Dict[str, str]], mode: str = "train", device=None,
-                 augment=None):
+                 augment=None, resize: bool = True):
         data = config["data"]
         self.rows, self.mode, self.mods = list(rows), mode, list(data["modalities"])
         self.root = Path(data["data_root"])
@@ -147,7 +147,8 @@ class DeviceNiftiDataset:
         self.label_dtype = LABEL_DTYPES[name]
         self.norm = DeviceModalityNormalize(config)
         img_size = config["model"].get("backbone", {}).get("img_size", [96, 96, 96])
-        self.resize = DeviceResize(img_size) if len(img_size) == 3 else None       # transforms.py:446-449
+        # transforms.py:446-449; resize=False (data.patch.enabled): volumes keep their own size
+        self.resize = DeviceResize(img_size) if resize and len(img_size) == 3 else None
         self.augment = augment if mode == "train" else None
         self._stager: Optional[HostStager] = None      # no GPU is touched before the first sample
 
@@ -175,7 +176,8 @@ class DeviceNiftiDataset:
             raise FileNotFoundError(f"{col} file of patient {row['patient_id']} not found: {p}")
         return p
 
-    def get(self, i: int, epoch: int) -> Dict[str, Any]:
+    def volume(self, i: int) -> Tuple[torch.Tensor, torch.Tensor, str]:
+        """Row i decoded and normalised at its own size: (image [M, X, Y, Z] fp32, label [X, Y, Z], patient_id)."""
         row = self.rows[i]
         paths = [self._path(row, mod) for mod in self.mods]
         image, first = load_modalities(paths, self.stager)
@@ -185,6 +187,11 @@ class DeviceNiftiDataset:
             raise ValueError(f"{lpath}: label shape {lh.shape} differs from {paths[0]}'s {first.shape}")
         label = decode_label(lh, self.stager.upload(lraw), self.label_dtype)
         self.norm(image)
+        return image, label, row["patient_id"]
+
+    def get(self, i: int, epoch: int) -> Dict[str, Any]:
+        row = self.rows[i]
+        image, label, _ = self.volume(i)
         sample = {"image": image, "label": label}
         if self.augment is not None:
             sample = self.augment(sample, epoch, i, self.seed)

@@ -396,11 +396,14 @@ class Trainer:
         hd, cm = self._extra_metrics()
         total = torch.zeros((), dtype=torch.float64, device=self.device)
         n = 0
+        # data.patch.enabled: the network trains on patches, so a full-size validation volume goes through the
+        # sliding windows of predict(); loss and metrics then run on the full-size logits
+        windows = bool((self.config["data"].get("patch") or {}).get("enabled", False))
         with torch.no_grad():
             for batch in self.val_loader:
                 images = batch["image"].to(self.device, non_blocking=True)
                 labels = batch["label"].to(self.device, non_blocking=True)
-                outputs = self.model(images)
+                outputs = self._sliding_window_inference(images) if windows else self.model(images)
                 total += self.criterion(outputs, labels).double()
                 if hd is None and cm is None:
                     dm.update_from_logits(outputs, labels)
